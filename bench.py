@@ -2,6 +2,12 @@
 """Throughput bench for the Bloom-filter hot path (insert_many + include_many?).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config nstar|1m|100m|10k]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  ``--full`` adds the rest:
+the host-API timing, the secondary workloads, the per-rank multi-GPU models, the reference's
+benchmark loops, the CPU baseline and the committed PMC counters.  ``--dump-outputs DIR`` writes
+what the last timed step returned as ``DIR/<name>.npy`` (``dump_outputs``).
 
 One step = one ``insert_many`` batch + one ``include_many?`` batch of B
 synthetic keys each (key family D: decimal strings of seeded uniform ints,
@@ -304,9 +310,45 @@ def auto_mode(world: int, m: int, k: int, config: str = "nstar") -> str:
     return "replicated" if world == 2 and reach_bytes <= (64 << 30) else "partitioned"
 
 
+DUMP_SAMPLE = 1 << 22     # --dump-outputs: elements kept of each large output (16 MiB as float32)
+# Distinct step batches kept in HBM by a single-GPU run (~0.57 GB each at 2^24 keys); a run of more
+# steps passes over them again, so --steps sets the number of timed steps at any size.
+MAX_RESIDENT_STEPS = 64
+
+
+def dump_outputs(path: str, f, out: torch.Tensor, any_new: torch.Tensor, next_digests, whole_filter: bool):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files.
+
+    * include_answers — the include? answers of the last step's batch (1.0 = "may be present");
+    * any_new — the insert's any_new answer of every step so far, warm-up first (1.0 = a bit flipped);
+    * next_insert_digests — pipelined steps: the SHA-1 words of the next insert batch that the last
+      include? call wrote, one row of 4 words per key (float64: a u32 does not fit a float32);
+    * filter_bytes — bytes of the filter's Redis string (the bitset a caller would export).
+    The large ones are a fixed sample: the same seeded positions in every run, so two builds run
+    with the same arguments can be compared file by file."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng([SEED, 0xD0])
+
+    def positions(n: int) -> torch.Tensor:
+        pos = np.arange(n) if n <= DUMP_SAMPLE else np.sort(rng.integers(0, n, size=DUMP_SAMPLE))
+        return torch.from_numpy(pos).to(out.device)
+
+    np.save(os.path.join(path, "include_answers.npy"),
+            out[positions(out.numel())].to(torch.float32).cpu().numpy())
+    np.save(os.path.join(path, "any_new.npy"), any_new.ne(0).to(torch.float32).cpu().numpy())
+    if next_digests is not None:
+        rows = next_digests[positions(next_digests.shape[0])[: DUMP_SAMPLE // 8]]
+        np.save(os.path.join(path, "next_insert_digests.npy"),
+                (rows.to(torch.int64) & 0xFFFFFFFF).to(torch.float64).cpu().numpy())
+    if whole_filter:
+        ptr, _ = f.device_bits()
+        bits = torch.as_tensor(_DevBytes(ptr, (f.reach_bits + 7) // 8), device=out.device)
+        np.save(os.path.join(path, "filter_bytes.npy"), bits[positions(bits.numel())].to(torch.float32).cpu().numpy())
+
+
 def time_config(pkg, D: Dist, name: str, steps: int, warmup: int, want_host=False, mode: str = "auto",
                 overlap: bool = True, pipeline: bool = False, comm_prefetch: bool = False,
-                replicated_insert: str = "auto"):
+                replicated_insert: str = "auto", want_data: bool = False, dump_dir: str = ""):
     n, p, batch, prefill = CONFIGS[name]
     B = pkg.Bloomfilter
     m = B.optimal_m(n, p)
@@ -335,7 +377,8 @@ def time_config(pkg, D: Dist, name: str, steps: int, warmup: int, want_host=Fals
         if prefill == "random":
             rng = np.random.default_rng([SEED, 99, D.rank])
             f.shard_import(rng.bytes(f.local_bits // 8))
-    batches = make_batches(n, batch, D.rank, warmup + steps, dev)
+    total = warmup + steps
+    batches = make_batches(n, batch, D.rank, min(total, MAX_RESIDENT_STEPS) if mode == "single" else total, dev)
     torch.cuda.synchronize()
     log("[%s] m=%d k=%d batch=%d setup %.1fs" % (name, m, k, batch, time.time() - t0))
     out = torch.empty(batch, dtype=torch.uint8, device=dev)
@@ -372,13 +415,13 @@ def time_config(pkg, D: Dist, name: str, steps: int, warmup: int, want_host=Fals
 
     # Every timed insert asks for any_new, the reference's !found that drives EXPIRE
     # (ruby.rb:61-62): one pre-zeroed flag word per step, so no memset joins the step.
-    flags = torch.zeros(len(batches), dtype=torch.int32, device=dev)
+    flags = torch.zeros(total, dtype=torch.int32, device=dev)
     fstep = [0]
 
     def any_new_ptr():
         i = fstep[0]
         fstep[0] = i + 1
-        return flags[i % len(batches)].data_ptr()
+        return flags[i % total].data_ptr()
 
     def insert(bt):
         ikb, iko = bt[0]
@@ -422,7 +465,8 @@ def time_config(pkg, D: Dist, name: str, steps: int, warmup: int, want_host=Fals
         nxt = (batches[(i + 1) % len(batches)][0] + (batch,)) if pf_prefetch else None
         out.copy_(pf.insert_include_dev(ikb, iko, batch, pkb, pko, batch, next_insert=nxt))
 
-    for i, bt in enumerate(batches[:warmup]):
+    for i in range(warmup):
+        bt = batches[i % len(batches)]
         if pf is None or not overlap:
             insert(bt)
             include(bt)
@@ -436,7 +480,8 @@ def time_config(pkg, D: Dist, name: str, steps: int, warmup: int, want_host=Fals
     ev = []
     host_wait0 = rf.host_wait_s if rf is not None else 0.0
     t_start = time.perf_counter()
-    for i, bt in enumerate(batches[warmup:], start=warmup):
+    for i in range(warmup, total):
+        bt = batches[i % len(batches)]
         e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         e[0].record(stream)
         if pf is None or not overlap:
@@ -470,7 +515,11 @@ def time_config(pkg, D: Dist, name: str, steps: int, warmup: int, want_host=Fals
     assert got[: batch // 2].all(), "false negative in the include? batch"
     any_new_steps = int(flags[:fstep[0]].ne(0).sum().item())
     if fstep[0] and prefill == "random":   # 2^24 fresh keys into a half-empty filter flip bits
-        assert any_new_steps == fstep[0], "an insert batch reported any_new = false"
+        fresh = min(fstep[0], len(batches))   # (a batch passed over again finds its bits set)
+        assert int(flags[:fresh].ne(0).sum().item()) == fresh, "an insert batch reported any_new = false"
+    if dump_dir and D.rank == 0:
+        dump_outputs(dump_dir, f, out, flags[:fstep[0]], digs[step_no[0] % 2] if pipeline else None,
+                     whole_filter=pf is None)
     fp_rate = float(got[batch // 2:].mean())
     Lmean = float(batches[-1][1][1][-1].item()) / batch
     P = batch * k
@@ -539,8 +588,10 @@ def time_config(pkg, D: Dist, name: str, steps: int, warmup: int, want_host=Fals
         "bitset_bytes": bitset,
         "any_new_requested": bool(fstep[0]), "any_new_steps": any_new_steps,
     }
-    ib, io = to_host(*batches[0][0])
-    pb, po = to_host(*batches[0][1])
+    ib = io = pb = po = None
+    if want_host or want_data:
+        ib, io = to_host(*batches[0][0])
+        pb, po = to_host(*batches[0][1])
     if want_host and pf is None:
         # PCIe-inclusive rate of the host-pointer entry points (pageable numpy keys + uint64
         # offsets in, answers out), after one warm-up call that sizes the pinned staging.
@@ -975,6 +1026,15 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="nstar", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else the bench measures: the host-API "
+                         "timing, the secondary workloads, the per-rank multi-GPU models, the reference's "
+                         "benchmark loops, the CPU baseline, and the committed PMC counters in the line "
+                         "(each can be dropped again with its --no-... option)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (include? answers, any_new, the next "
+                         "batch's SHA-1 words, the filter's bytes; seeded samples of the large ones) as "
+                         "DIR/<name>.npy, after the timed steps")
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--secondary", default="1m,1m_big,100m,10b,200b,lua_1m",
                     help="comma list of the secondary workloads (1-GPU runs): configs and lua_1m")
@@ -1022,11 +1082,16 @@ def main():
         log("bench: the process group has %d ranks, --gpus %d" % (world_seen, args.gpus))
         sys.exit(2)
     pkg = pkgload.load()
-    main_res, data = time_config(pkg, D, args.config, args.steps, args.warmup, want_host=(D.world == 1 and not args.no_host_api),
+    # a plain run times its steps and prints the line; everything else waits for --full
+    extras = args.full and D.world == 1
+    want_cpu = extras and not args.no_cpu_baseline
+    main_res, data = time_config(pkg, D, args.config, args.steps, args.warmup,
+                                  want_host=(extras and not args.no_host_api),
                                   mode=args.mode, overlap=not args.no_overlap, pipeline=bool(args.pipeline),
-                                  comm_prefetch=bool(args.comm_prefetch), replicated_insert=args.replicated_insert)
+                                  comm_prefetch=bool(args.comm_prefetch), replicated_insert=args.replicated_insert,
+                                  want_data=want_cpu, dump_dir=args.dump_outputs)
     secondary = {}
-    if D.world == 1 and not args.no_secondary:
+    if extras and not args.no_secondary:
         # 1m_big: the L2-resident 1M@1 % filter at 2^24-key batches (hash-bound; 1m's 2^20-key
         # batches are launch- and latency-bound)
         # every secondary runs the step `--config <name>` runs (pipelined unless --pipeline 0),
@@ -1044,15 +1109,15 @@ def main():
                                    "kernels": {kn: round(v["ms"], 4) for kn, v in r["kernels"].items()},
                                    "pmc": load_pmc(name)}
     models = None
-    if D.world == 1 and args.models and not args.no_secondary:
+    if extras and args.models and not args.no_secondary:
         single = {name: r["ms_per_step"] for name, r in secondary.items() if "ms_per_step" in r}
         single[args.config] = main_res["wall_s"] / args.steps * 1e3
         models = model_legs([x for x in args.models.split(",") if x and x != "none"], single)
     shapes = None
-    if D.world == 1 and not args.no_reference_shapes:
+    if extras and not args.no_reference_shapes:
         shapes = reference_shapes(pkg)
     cpu = None
-    if D.rank == 0 and D.world == 1 and not args.no_cpu_baseline:
+    if D.rank == 0 and want_cpu:
         cpu = cpu_baseline(data)
     D.close()
     if D.rank != 0:
@@ -1137,7 +1202,7 @@ def main():
                      "kernel_ms_rocprof": rp_ms, "rocprof_source": rp_src,
                      "frac_rocprof": (dom["algo_bytes"] / (rp_ms / 1e3) / HBM_PEAK)
                      if rp_ms and "algo_bytes" in dom else None},
-        "pmc": load_pmc(args.config),
+        "pmc": load_pmc(args.config) if args.full else None,
         "cpu_baseline": cpu,
         "ops": {"insert": ins, "include": inc},
         "kernels": kern,
