@@ -29,6 +29,10 @@
  *   bf_clear          Ruby#clear (DEL key_name)                      ruby.rb:33-35
  *   bf_export_redis    GET key_name — the Redis string SETBIT builds  ruby.rb:59 (SETBIT layout)
  *   bf_import_redis    SET key_name — load a string written by the ruby driver
+ *   bf_bitcount        BITCOUNT key_name — set bits of the string SETBIT builds      ruby.rb:59 (SETBIT layout)
+ *   bf_bitop           BITOP AND / OR key_name key_name other — two filters combined on the device
+ *   bf_bitcount_op     BITCOUNT of a BITOP AND / OR / XOR result, nothing stored
+ *   bf_estimate_count  distinct keys behind a bit count, under the probe law of        ruby.rb:51
  *   bf_optimal_m/_k    Redis::Bloomfilter.optimal_m / optimal_k       lib/redis/bloomfilter.rb:50-58
  *   bf_version         Redis::Bloomfilter.version                     lib/redis/bloomfilter/version.rb:6-8
  *
@@ -279,6 +283,68 @@ int  bf_export_range(bf_handle* h, uint64_t offset, uint64_t len, uint8_t* buf);
  * multi-device handle or a shard: BF_EINVAL, use bf_dirty_ranges). */
 int  bf_insert_many_changes(bf_handle* h, const uint8_t* key_bytes, const uint64_t* offsets, uint64_t n,
                             uint64_t* out_bits, uint64_t cap, uint64_t* count);
+
+/* ---- statistics and filter-to-filter combines.  The device bitset IS the Redis string the
+ *      ruby driver's SETBITs build (ruby.rb:59: bit o in byte o >> 3 under 0x80 >> (o & 7)), so
+ *      Redis's BITCOUNT and BITOP on that key have device forms that never move the string:
+ *
+ *   bf_bitcount        BITCOUNT key start end: the set bits of bytes [byte_start, byte_start +
+ *                      byte_len) of the string.  The range is clamped to the bitset
+ *                      (device_bytes of bf_info, zero past the reachable prefix); byte_len =
+ *                      UINT64_MAX means "to the end"; a start at or past the end counts 0.  On a
+ *                      shard handle the range is in the shard's local bytes (bf_shard_export's
+ *                      layout).  The count is 64-bit: a filter can hold more than 2^32 set bits.
+ *                      Multi-device handles: a replicated handle counts device 0, a partitioned
+ *                      one sums its shards, and takes the WHOLE string only (byte_start = 0 and
+ *                      byte_len reaching the end): any other range is BF_EINVAL there.
+ *   bf_bitop           BITOP AND / OR dst dst src: dst = dst OP src for two filters on one
+ *                      device.  Both handles must share m, k, the hash engine, shard_count,
+ *                      shard_index, shard_block_log2 and the HIP device (two shard handles of the
+ *                      same geometry combine like two whole filters); otherwise BF_EINVAL, the
+ *                      message naming the first field that differs, and dst is untouched.
+ *                      Encoder handles (no bitset), multi-device handles and BF_BITOP_XOR are
+ *                      BF_EINVAL.  NOT is not offered: it would set bits at or past m.
+ *                      *changed (nullable) = 1 iff a bit of dst flipped (0 -> 1 for OR, 1 -> 0
+ *                      for AND), which is what drives EXPIRE at ruby.rb:62; *set_bits (nullable)
+ *                      = BITCOUNT of the result.  dst == src is a no-op: changed = 0 and the
+ *                      current count.  With bf_track_dirty on, exactly the BF_DIRTY_BLOCK_BYTES
+ *                      blocks whose bytes changed are marked (src's map is untouched), so a
+ *                      write-through caller sends only those.  AND can SHORTEN the trimmed
+ *                      string; bf_dirty_ranges clips its ranges to the new length and SETRANGE
+ *                      never shrinks a key, so a caller that mirrors the filter to Redis must
+ *                      rewrite the key (DEL + SET, or SET) after an AND.
+ *                      Both handles' mutexes are taken together (no lock order to respect:
+ *                      concurrent bf_bitop(a, b) and bf_bitop(b, a) do not deadlock), the launch
+ *                      goes to dst's stream after BOTH handles' last launches, and becomes the
+ *                      last launch of both.
+ *   bf_bitcount_op     BITCOUNT of (a OP b) with nothing written: AND (intersection), OR (union,
+ *                      through bf_estimate_count the size of the union) and XOR (the Hamming
+ *                      distance: 0 iff two replicas hold the same filter).  XOR exists only in
+ *                      this counting form, a ^ b is not a filter.  The same pair rule as bf_bitop.
+ *   bf_bitcount_dev / bf_bitop_dev   the same on the caller's stream, results in device memory,
+ *                      no synchronisation: *d_set_bits (8 bytes, nullable for bf_bitop_dev) is
+ *                      WRITTEN (zeroed on the stream, then summed); d_changed (nullable) gets 1
+ *                      ORed in like d_any_new of bf_insert_many_dev.  BF_EINVAL on a
+ *                      multi-device handle, as every *_dev call.
+ *   bf_estimate_count  how many distinct keys a filter of m_bits and k with set_bits bits set
+ *                      holds (host-only double arithmetic, like bf_optimal_m; flags = the
+ *                      filter's bf_config.flags).  With an engine flag the probes are uniform on
+ *                      [0, m) and this is the textbook -(m / k) ln(1 - X / m).  The ruby
+ *                      derivation is not uniform (ruby.rb:51: probe 0 never passes 2^32 and probe
+ *                      i is a trapezoid over [0, (i + 1) 2^32), each folded mod m), so the
+ *                      estimate inverts the expected count under that probe law, E(n) = integral
+ *                      of 1 - exp(-n lambda(b)) with lambda the sum of the k folded densities
+ *                      (DESIGN.md).  set_bits = 0 gives 0; set_bits >= the reachable bits gives
+ *                      +HUGE_VAL with BF_OK; set_bits > m_bits is BF_EINVAL. */
+#define BF_BITOP_AND 0u
+#define BF_BITOP_OR  1u
+#define BF_BITOP_XOR 2u   /* bf_bitcount_op only */
+int  bf_bitcount(bf_handle* h, uint64_t byte_start, uint64_t byte_len, uint64_t* set_bits);
+int  bf_bitcount_dev(bf_handle* h, uint64_t byte_start, uint64_t byte_len, uint64_t* d_set_bits, void* stream);
+int  bf_bitop(bf_handle* dst, uint32_t op, bf_handle* src, uint8_t* changed, uint64_t* set_bits);
+int  bf_bitop_dev(bf_handle* dst, uint32_t op, bf_handle* src, uint32_t* d_changed, uint64_t* d_set_bits, void* stream);
+int  bf_bitcount_op(bf_handle* a, uint32_t op, bf_handle* b, uint64_t* set_bits);
+int  bf_estimate_count(uint64_t m_bits, uint32_t k, uint32_t flags, uint64_t set_bits, double* n_hat);
 
 /* ---- per-kernel timing.  While enabled, every keyed launch (insert / include? /
  *      indexes, host or device API) records HIP events on its stream between its

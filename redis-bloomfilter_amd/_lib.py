@@ -19,6 +19,7 @@ DEFAULT_LIB = os.path.join(PKG_DIR, "lib", "libbfhip.so")
 
 BF_OK, BF_EINVAL, BF_ENOMEM, BF_EDEVICE, BF_ERCCL, BF_ERANGE = 0, 1, 2, 3, 4, 5
 BF_IMPORT_REPLACE, BF_IMPORT_OR = 0, 1
+BF_BITOP_AND, BF_BITOP_OR, BF_BITOP_XOR = 0, 1, 2   # XOR: bitcount_op only
 BF_FLAG_ROUTE32 = 1
 BF_FLAG_ENGINE_MD5, BF_FLAG_ENGINE_SHA1 = 2, 4   # RubyTest hash engines (ruby_test.rb:43-61)
 BF_FLAG_ENCODER = 8   # no bitset: region-set encodes only (a replicated filter's second, encoding handle)
@@ -100,6 +101,12 @@ SIGNATURES = {
     "bf_dirty_ranges": (ctypes.c_int, [_vp, _u64p, _u32, _u32p, _u64p, _u32]),
     "bf_export_range": (ctypes.c_int, [_vp, _u64, _u64, _vp]),
     "bf_insert_many_changes": (ctypes.c_int, [_vp, _vp, _vp, _u64, _vp, _u64, _u64p]),
+    "bf_bitcount": (ctypes.c_int, [_vp, _u64, _u64, _u64p]),
+    "bf_bitcount_dev": (ctypes.c_int, [_vp, _u64, _u64, _vp, _vp]),
+    "bf_bitop": (ctypes.c_int, [_vp, _u32, _vp, _u8p, _u64p]),
+    "bf_bitop_dev": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp, _vp]),
+    "bf_bitcount_op": (ctypes.c_int, [_vp, _u32, _vp, _u64p]),
+    "bf_estimate_count": (ctypes.c_int, [_u64, _u32, _u32, _u64, ctypes.POINTER(ctypes.c_double)]),
     "bf_profile": (ctypes.c_int, [_vp, _u32]),
     "bf_profile_read": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u32, _u32p, _u32]),
     "bf_sync": (ctypes.c_int, [_vp]),
@@ -220,6 +227,34 @@ def optimal_m(n, error_rate) -> int:
 
 def optimal_k(n: int, m: int) -> int:
     return int(load().bf_optimal_k(int(n), int(m)))
+
+
+def estimate_count(m: int, k: int, set_bits: int, flags: int = 0) -> float:
+    """Distinct keys behind ``set_bits`` set bits of a filter of m bits and k hashes
+    (bf_estimate_count): the expected-count model of the ruby derivation's probe law
+    (ruby.rb:51), or the textbook -(m/k) ln(1 - X/m) with a BF_FLAG_ENGINE_* flag.  Host-only.
+    ``inf`` for a full filter; ArgumentError when set_bits > m."""
+    if not 0 <= int(set_bits) < 1 << 64 or not 0 < int(m) < 1 << 64:
+        raise ArgumentError("estimate_count: m and set_bits must be unsigned 64-bit (m > 0)")
+    out = ctypes.c_double()
+    rc = load().bf_estimate_count(int(m), int(k), int(flags), int(set_bits), ctypes.byref(out))
+    if rc:
+        raise ArgumentError("bf_estimate_count(m=%r, k=%r, set_bits=%r): set_bits must be <= m and k in [1, %d]"
+                            % (m, k, set_bits, BF_MAX_K))
+    return float(out.value)
+
+
+_OPS = {"and": BF_BITOP_AND, "or": BF_BITOP_OR, "xor": BF_BITOP_XOR}
+_U64_MAX = (1 << 64) - 1
+
+
+def _op(op) -> int:
+    """BF_BITOP_* from the constant or its name ('and' / 'or' / 'xor', any case)."""
+    if isinstance(op, str):
+        if op.lower() not in _OPS:
+            raise ArgumentError("op must be 'and', 'or' or 'xor', got %r" % (op,))
+        return _OPS[op.lower()]
+    return int(op)
 
 
 def indexes(key: bytes, m: int, k: int) -> List[int]:
@@ -431,6 +466,59 @@ class Filter:
         buf = np.zeros(max(int(length), 1), np.uint8)
         _check(self._lib.bf_export_range(self.handle, int(offset), int(length), _ptr(buf)), self._h)
         return buf[: int(length)].tobytes()
+
+    # -- statistics and filter-to-filter combines (Redis BITCOUNT / BITOP on the device string)
+    def bitcount_bytes(self, byte_start: int = 0, byte_len: int = _U64_MAX) -> int:
+        """Set bits of bytes [byte_start, byte_start + byte_len) (bf_bitcount: clamped to the
+        bitset; the default counts everything; a shard handle counts its local bytes)."""
+        n = ctypes.c_uint64()
+        _check(self._lib.bf_bitcount(self.handle, int(byte_start), min(int(byte_len), _U64_MAX), ctypes.byref(n)),
+               self._h)
+        return int(n.value)
+
+    def bitcount(self, start: int = 0, end: int = -1) -> int:
+        """Redis ``BITCOUNT key start end``: inclusive byte indices, negative ones counting from
+        the end of the trimmed string (only those cost a ``redis_len()``; ``end=-1`` alone does
+        not, the bytes past the string are zero)."""
+        start, end = int(start), int(end)
+        if start >= 0 and end == -1:
+            return self.bitcount_bytes(start)
+        if start < 0 or end < 0:
+            n = self.redis_len()
+            if start < 0 and end < 0 and start > end:
+                return 0
+            start = max(start + n, 0) if start < 0 else start
+            end = max(end + n, 0) if end < 0 else end
+            end = min(end, n - 1)
+        if start > end:
+            return 0
+        return self.bitcount_bytes(start, end - start + 1)
+
+    def bitcount_dev(self, d_set_bits: int, byte_start: int = 0, byte_len: int = _U64_MAX, stream=None) -> None:
+        """bitcount_bytes on ``stream`` without a sync; the uint64 at d_set_bits is written."""
+        _check(self._lib.bf_bitcount_dev(self.handle, int(byte_start), min(int(byte_len), _U64_MAX), d_set_bits,
+                                         self._s(stream)), self._h)
+
+    def bitop(self, op, other: "Filter") -> Tuple[bool, int]:
+        """self = self OP other ('and' / 'or'), both on one device with the same geometry
+        (bf_bitop) -> (changed, set bits of the result).  With dirty tracking on, exactly the
+        blocks that changed are marked."""
+        ch, n = ctypes.c_uint8(0), ctypes.c_uint64()
+        _check(self._lib.bf_bitop(self.handle, _op(op), other.handle, ctypes.byref(ch), ctypes.byref(n)), self._h)
+        return bool(ch.value), int(n.value)
+
+    def bitop_dev(self, op, other: "Filter", d_changed: int = 0, d_set_bits: int = 0, stream=None) -> None:
+        """bitop on ``stream`` without a sync: 1 is ORed into the uint32 at d_changed when a bit
+        changed, the uint64 at d_set_bits is written (both optional)."""
+        _check(self._lib.bf_bitop_dev(self.handle, _op(op), other.handle, d_changed or None, d_set_bits or None,
+                                      self._s(stream)), self._h)
+
+    def bitcount_op(self, op, other: "Filter") -> int:
+        """Set bits of (self OP other), 'and' / 'or' / 'xor' (the Hamming distance), with
+        neither filter modified (bf_bitcount_op)."""
+        n = ctypes.c_uint64()
+        _check(self._lib.bf_bitcount_op(self.handle, _op(op), other.handle, ctypes.byref(n)), self._h)
+        return int(n.value)
 
     # -- device-resident API
     def insert_many_dev(self, d_keys: int, d_offsets: int, n: int, d_any_new: int = 0,

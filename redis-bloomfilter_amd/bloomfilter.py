@@ -148,3 +148,28 @@ class Bloomfilter:
         if hasattr(self.driver, "include_many"):
             return self.driver.include_many(keys)
         return [self.driver.include(k) for k in keys]
+
+    # statistics and merging (the hip drivers: BITCOUNT / BITOP OR on the device string)
+    def _driver_method(self, name):
+        fn = getattr(self.driver, name, None)
+        if fn is None:
+            raise NotImplementedError("driver '%s' has no %s" % (self.options["driver"], name))
+        return fn
+
+    def count_bits(self) -> int:
+        return self._driver_method("count_bits")()
+
+    def fill_ratio(self) -> float:
+        return self._driver_method("fill_ratio")()
+
+    def estimated_size(self) -> float:
+        return self._driver_method("estimated_size")()
+
+    def merge(self, other: "Bloomfilter", expire=None) -> bool:
+        return self._driver_method("merge")(other.driver, self._expire(expire))
+
+    def union_size(self, other: "Bloomfilter") -> float:
+        return self._driver_method("union_size")(other.driver)
+
+    def intersection_size(self, other: "Bloomfilter") -> float:
+        return self._driver_method("intersection_size")(other.driver)

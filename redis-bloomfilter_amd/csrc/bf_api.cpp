@@ -2502,3 +2502,165 @@ int bf_insert_plan(const bf_handle* h, uint64_t n, uint32_t* binned, uint64_t* s
 }
 
 }  // extern "C"
+
+// ---- statistics and filter-to-filter combines (bf_stats.hip) --------------------------------
+
+namespace {
+
+// The result words of the synchronous forms: d_scan[1] (the 64-bit count) and the low half of
+// d_scan[2] (changed), read back together through the pinned h_flag + 4.  Written only by
+// launches made under the handle's mutex and ordered by StreamOrder, like d_scan[0].
+constexpr int kStatWord = 1;        // index into d_scan
+constexpr int kStatFlagWord = 4;    // index into h_flag (uint32): 16 bytes in
+
+// Counts bytes [start, start + len) clamped to the bitset into *d_out (zeroed on s first).
+int launch_bitcount(bf_handle* h, uint64_t start, uint64_t len, unsigned long long* d_out, hipStream_t s) {
+    HIPCHK(h, hipMemsetAsync(d_out, 0, sizeof(unsigned long long), s));
+    if (start >= h->dev_bytes) return BF_OK;
+    len = std::min(len, h->dev_bytes - start);
+    HIPCHK(h, bf_launch_bitcount(h->g.bits, start, len, d_out, s));
+    return BF_OK;
+}
+
+int read_stat_words(bf_handle* h, uint64_t* count, uint8_t* changed) {
+    HIPCHK(h, hipMemcpyAsync(h->h_flag + kStatFlagWord, h->d_scan + kStatWord, 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (count) memcpy(count, h->h_flag + kStatFlagWord, sizeof *count);
+    if (changed) *changed = h->h_flag[kStatFlagWord + 2] ? 1 : 0;
+    return BF_OK;
+}
+
+const char* engine_name(uint32_t e) { return e == BF_ENGINE_MD5 ? "md5" : (e == BF_ENGINE_SHA1 ? "sha1" : "ruby"); }
+
+// bf_bitop / bf_bitcount_op take two handles that hold the same bits of the same filter on one
+// device; the message names the first field that differs.  Caller holds both mutexes.
+int check_pair(bf_handle* a, const bf_handle* b, const char* fn) {
+    if (!a->g.bits || !b->g.bits)
+        return set_err(a, BF_EINVAL, "%s: an encoder handle (BF_FLAG_ENCODER) holds no bitset", fn);
+    if (a->m != b->m)
+        return set_err(a, BF_EINVAL, "%s: the filters differ in m (%llu vs %llu)", fn, (unsigned long long)a->m,
+                       (unsigned long long)b->m);
+    if (a->k != b->k) return set_err(a, BF_EINVAL, "%s: the filters differ in k (%u vs %u)", fn, a->k, b->k);
+    if (a->engine != b->engine)
+        return set_err(a, BF_EINVAL, "%s: the filters differ in hash engine (%s vs %s)", fn, engine_name(a->engine),
+                       engine_name(b->engine));
+    if (a->shards != b->shards)
+        return set_err(a, BF_EINVAL, "%s: the handles differ in shard_count (%u vs %u)", fn, a->shards, b->shards);
+    if (a->shard_index != b->shard_index)
+        return set_err(a, BF_EINVAL, "%s: the handles differ in shard_index (%u vs %u)", fn, a->shard_index,
+                       b->shard_index);
+    if (a->block_log2 != b->block_log2)
+        return set_err(a, BF_EINVAL, "%s: the handles differ in shard_block_log2 (%u vs %u)", fn, a->block_log2,
+                       b->block_log2);
+    if (a->device != b->device)
+        return set_err(a, BF_EINVAL, "%s: the handles differ in device (%d vs %d)", fn, a->device, b->device);
+    return BF_OK;
+}
+
+// body(s) with both handles locked (together: no lock order), checked as a pair, their device
+// current and the launch stream s ordered after BOTH handles' last launches; what body
+// enqueues becomes the last launch of both.  a == b: one lock, one order.
+template <typename F>
+int with_pair(bf_handle* a, bf_handle* b, const char* fn, bool own_stream, void* stream, F&& body) {
+    if (!a || !b) return BF_EINVAL;
+    if (a->multi) return bfm_fail(a->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
+    auto run = [&](bool two) -> int {
+        if (b->multi) return set_err(a, BF_EINVAL, "%s: the other handle is a multi-device handle", fn);
+        if (int rc = check_pair(a, b, fn)) return rc;
+        DeviceGuard dg(a->device);
+        if (!dg.ok) return set_err(a, BF_EDEVICE, "hipSetDevice(%d) failed", a->device);
+        const hipStream_t s = own_stream ? a->stream : reinterpret_cast<hipStream_t>(stream);
+        StreamOrder so_a(a, s);
+        if (int krc = op_check(a)) return krc;
+        if (!two) return body(s);
+        StreamOrder so_b(b, s);
+        if (int krc = op_check(b)) return set_err(a, krc, "%s: the other handle: %s", fn, b->err.c_str());
+        return body(s);
+    };
+    if (a == b) {
+        std::lock_guard<std::mutex> lk(a->mu);
+        return run(false);
+    }
+    if (b->multi) {   // its bf_handle is a shell: nothing of it to lock
+        std::lock_guard<std::mutex> lk(a->mu);
+        return run(false);
+    }
+    std::scoped_lock lk(a->mu, b->mu);   // deadlock-free for (a, b) against (b, a)
+    return run(true);
+}
+
+int bitop_impl(bf_handle* dst, uint32_t op, bf_handle* src, bool own_stream, void* stream, uint32_t* d_changed,
+               uint64_t* d_set_bits, uint8_t* changed, uint64_t* set_bits) {
+    return with_pair(dst, src, "bf_bitop", own_stream, stream, [&](hipStream_t s) -> int {
+        if (op != BF_BITOP_AND && op != BF_BITOP_OR)
+            return set_err(dst, BF_EINVAL, "bf_bitop: op must be BF_BITOP_AND or BF_BITOP_OR, got %u (XOR only "
+                                           "counts: bf_bitcount_op)", op);
+        unsigned long long* d_count = reinterpret_cast<unsigned long long*>(d_set_bits);
+        if (own_stream) {
+            d_count = dst->d_scan + kStatWord;
+            d_changed = reinterpret_cast<uint32_t*>(dst->d_scan + kStatWord + 1);
+            HIPCHK(dst, hipMemsetAsync(d_count, 0, 16, s));
+        } else if (d_count) {
+            HIPCHK(dst, hipMemsetAsync(d_count, 0, sizeof *d_count, s));
+        }
+        if (dst == src) {   // x OP x = x: nothing changes
+            if (d_count) HIPCHK(dst, bf_launch_bitcount(dst->g.bits, 0, dst->dev_bytes, d_count, s));
+        } else {
+            HIPCHK(dst, bf_launch_bitop(op, dst->g.bits, src->g.bits, dst->dev_bytes / 4, dst->g.dirty, d_changed,
+                                        d_count, s));
+        }
+        return own_stream ? read_stat_words(dst, set_bits, changed) : BF_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int bf_bitcount(bf_handle* h, uint64_t byte_start, uint64_t byte_len, uint64_t* set_bits) {
+    if (h && h->multi) return set_bits ? bfm_bitcount(h->multi, byte_start, byte_len, set_bits) : BF_EINVAL;
+    if (!h || !set_bits) return BF_EINVAL;
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard dg(h->device);
+    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
+    StreamOrder so(h, h->stream);
+    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
+    if (int rc = launch_bitcount(h, byte_start, byte_len, h->d_scan + kStatWord, h->stream)) return rc;
+    return read_stat_words(h, set_bits, nullptr);
+}
+
+int bf_bitcount_dev(bf_handle* h, uint64_t byte_start, uint64_t byte_len, uint64_t* d_set_bits, void* stream) {
+    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
+    if (!h) return BF_EINVAL;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!d_set_bits) return set_err(h, BF_EINVAL, "d_set_bits is NULL");
+    DeviceGuard dg(h->device);
+    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
+    StreamOrder so(h, reinterpret_cast<hipStream_t>(stream));
+    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
+    return launch_bitcount(h, byte_start, byte_len, reinterpret_cast<unsigned long long*>(d_set_bits), so.s);
+}
+
+int bf_bitop(bf_handle* dst, uint32_t op, bf_handle* src, uint8_t* changed, uint64_t* set_bits) {
+    return bitop_impl(dst, op, src, true, nullptr, nullptr, nullptr, changed, set_bits);
+}
+
+int bf_bitop_dev(bf_handle* dst, uint32_t op, bf_handle* src, uint32_t* d_changed, uint64_t* d_set_bits,
+                 void* stream) {
+    return bitop_impl(dst, op, src, false, stream, d_changed, d_set_bits, nullptr, nullptr);
+}
+
+int bf_bitcount_op(bf_handle* a, uint32_t op, bf_handle* b, uint64_t* set_bits) {
+    if (!set_bits) return BF_EINVAL;
+    return with_pair(a, b, "bf_bitcount_op", true, nullptr, [&](hipStream_t s) -> int {
+        if (op != BF_BITOP_AND && op != BF_BITOP_OR && op != BF_BITOP_XOR)
+            return set_err(a, BF_EINVAL, "bf_bitcount_op: op must be BF_BITOP_AND, _OR or _XOR, got %u", op);
+        unsigned long long* d_count = a->d_scan + kStatWord;
+        HIPCHK(a, hipMemsetAsync(d_count, 0, sizeof *d_count, s));
+        if (a != b) HIPCHK(a, bf_launch_bitcount_op(op, a->g.bits, b->g.bits, a->dev_bytes / 4, d_count, s));
+        else if (op != BF_BITOP_XOR) HIPCHK(a, bf_launch_bitcount(a->g.bits, 0, a->dev_bytes, d_count, s));   // x ^ x = 0
+        return read_stat_words(a, set_bits, nullptr);
+    });
+}
+
+}  // extern "C"

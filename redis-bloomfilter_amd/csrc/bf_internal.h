@@ -380,6 +380,20 @@ hipError_t bf_launch_last_nonzero(const uint32_t* words, uint64_t nwords,
 // dst[i] |= src[i] for i < nwords (nwords multiple of 4, both 16-byte aligned).
 hipError_t bf_launch_or(uint32_t* dst, const uint32_t* src, uint64_t nwords, hipStream_t s);
 
+// Statistics and filter-to-filter combines (bf_stats.hip).  op: BF_BITOP_* of bfhip.h.
+// *d_count += set bits of bytes [byte_start, byte_start + byte_len) (inside the bitset; device
+// byte b is bits 8 (b & 3).. of word b >> 2).  d_count must be zeroed before the launch.
+hipError_t bf_launch_bitcount(const uint32_t* bits, uint64_t byte_start, uint64_t byte_len,
+                              unsigned long long* d_count, hipStream_t s);
+// *d_count += popcount(a OP b) over nwords (a multiple of 4, both 16-byte aligned); AND, OR, XOR.
+hipError_t bf_launch_bitcount_op(uint32_t op, const uint32_t* a, const uint32_t* b, uint64_t nwords,
+                                 unsigned long long* d_count, hipStream_t s);
+// dst = dst OP src (AND, OR; dst != src) over nwords; only vectors that change are stored.
+// Nullable: dirty (the bf_track_dirty map: exactly the blocks that changed are marked),
+// d_changed (1 ORed in when any bit changed), d_count (+= popcount of the result; zeroed before).
+hipError_t bf_launch_bitop(uint32_t op, uint32_t* dst, const uint32_t* src, uint64_t nwords, uint8_t* dirty,
+                           uint32_t* d_changed, unsigned long long* d_count, hipStream_t s);
+
 // out[i] = in[i] (uint32 -> uint64), i < count: the host-pointer calls' relative offsets.
 hipError_t bf_launch_widen_offsets(const uint32_t* in, uint64_t* out, uint64_t count, hipStream_t s);
 

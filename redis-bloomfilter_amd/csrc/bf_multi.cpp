@@ -554,6 +554,23 @@ int bfm_sync(BfMulti* mh) {
     return each_device(mh, [&](uint32_t d) { return bf_sync(mh->sub[d]); });
 }
 
+int bfm_bitcount(BfMulti* mh, uint64_t byte_start, uint64_t byte_len, uint64_t* set_bits) {
+    std::lock_guard<std::mutex> lk(mh->mu);
+    if (mh->mode == BF_MODE_REPLICATED || mh->D == 1)
+        return sub_rc(mh, 0, bf_bitcount(mh->sub[0], byte_start, byte_len, set_bits));
+    // a byte range of the string is scattered over the shards' blocks: only the whole string sums
+    if (byte_start != 0 || byte_len < (mh->reach + 7) / 8)
+        return fail(mh, BF_EINVAL, "bf_bitcount on a partitioned multi-device handle counts the whole string only "
+                                   "(byte_start 0, byte_len to the end)");
+    std::vector<uint64_t> part(mh->D, 0);
+    int rc = each_device(mh, [&](uint32_t d) { return bf_bitcount(mh->sub[d], 0, UINT64_MAX, &part[d]); });
+    if (rc) return rc;
+    uint64_t total = 0;
+    for (uint64_t p : part) total += p;
+    *set_bits = total;
+    return BF_OK;
+}
+
 int bfm_insert_plan(const BfMulti* mh, uint64_t n, uint32_t* binned, uint64_t* scratch_bytes) {
     return bf_insert_plan(mh->sub[0], n, binned, scratch_bytes);
 }

@@ -29,6 +29,8 @@ int bfm_track_dirty(BfMulti* mh, uint32_t enable);
 int bfm_dirty_ranges(BfMulti* mh, uint64_t* ranges, uint32_t cap, uint32_t* n_out, uint64_t* redis_len,
                      uint32_t clear);
 int bfm_export_range(BfMulti* mh, uint64_t offset, uint64_t len, uint8_t* buf);
+// replicated: device 0's count; partitioned: the shards' sum, whole string only
+int bfm_bitcount(BfMulti* mh, uint64_t byte_start, uint64_t byte_len, uint64_t* set_bits);
 int bfm_insert_plan(const BfMulti* mh, uint64_t n, uint32_t* binned, uint64_t* scratch_bytes);
 int bfm_fail(BfMulti* mh, int code, const char* msg);
 

@@ -17,7 +17,11 @@ HBM (one ``bf_handle``); Redis keeps the same bitstring the ruby driver writes:
   ``flush()`` / ``reload()``; ``flush()`` writes what changed since the last
   one (``flush(full=True)``: the whole string);
 * TTL: the device copy is cleared when the mirrored EXPIRE deadline passes,
-  as the Redis key would have vanished (README.md usage, ruby.rb:62).
+  as the Redis key would have vanished (README.md usage, ruby.rb:62);
+* statistics and merging: ``count_bits`` / ``fill_ratio`` / ``estimated_size`` (BITCOUNT on
+  the device string, through ``bf_estimate_count``), ``merge(other, expire)`` (BITOP OR of two
+  device filters; write-through sends exactly the changed blocks) and ``union_size`` /
+  ``intersection_size``, which modify neither filter.
 
 Strings beyond one request: every write is cut into SETRANGE calls of at most
 ``chunk_bytes`` (default 8 MiB) and a key longer than that is read back with
@@ -40,7 +44,7 @@ from typing import Iterable, Optional
 import numpy as np
 
 from .. import keys as _keys
-from .._lib import ArgumentError, BF_IMPORT_REPLACE, DIRTY_BLOCK_BYTES, Filter
+from .._lib import ArgumentError, BF_BITOP_OR, BF_IMPORT_REPLACE, DIRTY_BLOCK_BYTES, Filter, estimate_count
 
 
 class Hip:
@@ -61,7 +65,7 @@ class Hip:
         devices = options.get("devices")
         if isinstance(devices, int):   # `devices: 8` -> the first 8 GPUs
             devices = list(range(devices))
-        flags = self._filter_flags()
+        flags = self._flags = self._filter_flags()
         self.filter = Filter(m, k, device=options.get("device", -1),
                              batch_keys=options.get("batch_keys", 0),
                              batch_bytes=options.get("batch_bytes", 0),
@@ -206,6 +210,60 @@ class Hip:
         self._deadline = None
         if self._redis is not None:
             self._redis.delete(self.key_name)
+
+    # -- statistics (Redis BITCOUNT on the device string) and merging (BITOP OR)
+    def count_bits(self) -> int:
+        """BITCOUNT key_name, counted on the device."""
+        self._expired()
+        return self.filter.bitcount()
+
+    def fill_ratio(self) -> float:
+        return self.count_bits() / float(self.options["bits"])
+
+    def _estimate(self, set_bits: int) -> float:
+        return estimate_count(self.options["bits"], self.options["hashes"], set_bits, self._flags)
+
+    def estimated_size(self) -> float:
+        """About how many distinct keys the filter holds: the bit count through the probe law
+        of this driver's derivation (bf_estimate_count), not the textbook uniform formula."""
+        return self._estimate(self.count_bits())
+
+    def _check_mergeable(self, other) -> None:
+        if not isinstance(other, Hip):
+            raise ArgumentError("the other filter's driver must be a hip driver, got %s" % type(other).__name__)
+        for what, mine, theirs in (("bits", self.options["bits"], other.options["bits"]),
+                                   ("hashes", self.options["hashes"], other.options["hashes"]),
+                                   ("hash engine", self._flags, other._flags)):
+            if mine != theirs:
+                raise ArgumentError("the filters differ in %s (%r vs %r)" % (what, mine, theirs))
+
+    def merge(self, other: "Hip", expire=None) -> bool:
+        """OR ``other``'s filter into this one (BITOP OR key_name key_name other) on the device;
+        True iff some bit flipped.  Write-through then sends exactly the 64 KiB blocks that
+        changed, and ``expire`` is armed as by an insert that set a bit (ruby.rb:62)."""
+        self._check_mergeable(other)
+        self._expired()
+        other._expired()
+        changed, _ = self.filter.bitop(BF_BITOP_OR, other.filter)
+        if changed:
+            if self._redis is not None and self.sync_mode == "write_through":
+                self.flush()
+            if expire is not None and expire is not False:
+                self._arm(expire)
+        return changed
+
+    def union_size(self, other: "Hip") -> float:
+        """Estimated distinct keys of both filters together; neither is modified."""
+        self._check_mergeable(other)
+        self._expired()
+        other._expired()
+        return self._estimate(self.filter.bitcount_op(BF_BITOP_OR, other.filter))
+
+    def intersection_size(self, other: "Hip") -> float:
+        """Estimated keys the two filters share, by inclusion-exclusion on the three estimates
+        n(A) + n(B) - n(A or B); neither filter is modified."""
+        union = self.union_size(other)
+        return self._estimate(self.filter.bitcount()) + other._estimate(other.filter.bitcount()) - union
 
     # -- Redis sync
     def flush(self, full: bool = False) -> int:

@@ -82,6 +82,18 @@ class Redis
       attach_function :bf_insert_many_changes, %i[pointer pointer pointer uint64 pointer uint64 pointer], :int,
                       blocking: true
       attach_function :bf_indexes, %i[pointer uint64 uint64 uint32 pointer], :int, blocking: true
+      # BITCOUNT / BITOP on the device string and the size estimate (include/bfhip.h)
+      attach_function :bf_bitcount, %i[pointer uint64 uint64 pointer], :int, blocking: true
+      attach_function :bf_bitcount_dev, %i[pointer uint64 uint64 pointer pointer], :int, blocking: true
+      attach_function :bf_bitop, %i[pointer uint32 pointer pointer pointer], :int, blocking: true
+      attach_function :bf_bitop_dev, %i[pointer uint32 pointer pointer pointer pointer], :int, blocking: true
+      attach_function :bf_bitcount_op, %i[pointer uint32 pointer pointer], :int, blocking: true
+      attach_function :bf_estimate_count, %i[uint64 uint32 uint32 uint64 pointer], :int
+
+      BF_BITOP_AND = 0
+      BF_BITOP_OR = 1
+      BF_BITOP_XOR = 2
+      UINT64_MAX = 0xFFFFFFFFFFFFFFFF
     end
 
     class Hip
@@ -163,6 +175,59 @@ class Redis
         @redis&.del(@options[:key_name])
       end
 
+      # BITCOUNT key_name, counted on the device (bf_bitcount).
+      def count_bits
+        expire_if_due
+        out = FFI::MemoryPointer.new(:uint64)
+        check(HipFFI.bf_bitcount(@handle, 0, HipFFI::UINT64_MAX, out))
+        out.read_uint64
+      end
+
+      def fill_ratio
+        count_bits.to_f / @options[:bits]
+      end
+
+      # About how many distinct keys the filter holds (bf_estimate_count: the probe law of
+      # this driver's derivation, ruby.rb:51, not the textbook uniform formula).
+      def estimated_size
+        estimate(count_bits)
+      end
+
+      # BITOP OR key_name key_name other, on the device; true iff some bit flipped.
+      # Write-through then sends exactly the changed 64 KiB blocks; EXPIRE as ruby.rb:62.
+      def merge(other, expire = nil)
+        check_mergeable(other)
+        expire_if_due
+        other.sync_expiry
+        flag = FFI::MemoryPointer.new(:uint8)
+        check(HipFFI.bf_bitop(@handle, HipFFI::BF_BITOP_OR, other.handle, flag, nil))
+        changed = flag.read_uint8 == 1
+        if changed
+          flush if @redis && @sync == :write_through
+          if expire
+            @deadline = now + expire
+            @redis.expire(@options[:key_name], expire) if @redis && @sync == :write_through
+          end
+        end
+        changed
+      end
+
+      # Estimated distinct keys of both filters together; neither is modified.
+      def union_size(other)
+        check_mergeable(other)
+        expire_if_due
+        other.sync_expiry
+        out = FFI::MemoryPointer.new(:uint64)
+        check(HipFFI.bf_bitcount_op(@handle, HipFFI::BF_BITOP_OR, other.handle, out))
+        estimate(out.read_uint64)
+      end
+
+      # Estimated keys the filters share: n(A) + n(B) - n(A or B).
+      def intersection_size(other)
+        union = union_size(other)
+        estimated_size + other.estimated_size - union
+      end
+
       # Device changes -> Redis, one SETRANGE per dirty range (keeps the TTL, grows
       # like SETBIT); full: true sends the whole string.  Returns the bytes sent.
       def flush(full: false)
@@ -226,6 +291,29 @@ class Redis
       end
 
       protected
+
+      # What another Hip driver needs of this one for merge / union_size.
+      attr_reader :handle, :options
+
+      def sync_expiry
+        expire_if_due
+      end
+
+      def estimate(set_bits)
+        out = FFI::MemoryPointer.new(:double)
+        rc = HipFFI.bf_estimate_count(@options[:bits], @options[:hashes], config_flags, set_bits, out)
+        raise ArgumentError, "bf_estimate_count: #{set_bits} set bits exceed the filter" unless rc == HipFFI::BF_OK
+
+        out.read_double
+      end
+
+      def check_mergeable(other)
+        raise ArgumentError, 'the other filter must use a hip driver' unless other.is_a?(Hip)
+
+        mine = [@options[:bits], @options[:hashes], config_flags]
+        theirs = [other.options[:bits], other.options[:hashes], other.config_flags]
+        raise ArgumentError, "the filters differ in bits, hashes or hash engine (#{mine} vs #{theirs})" if mine != theirs
+      end
 
       # Ruby#indexes_for (ruby.rb:41-55): the k offsets of one key, from the device kernel.
       def indexes_for(data)
