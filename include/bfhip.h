@@ -33,6 +33,8 @@
  *   bf_bitop           BITOP AND / OR key_name key_name other — two filters combined on the device
  *   bf_bitcount_op     BITCOUNT of a BITOP AND / OR / XOR result, nothing stored
  *   bf_estimate_count  distinct keys behind a bit count, under the probe law of        ruby.rb:51
+ *   bf_bank_*          many filters of one (m, k), one per key_name, behind one handle:
+ *                      Ruby#insert / #include? / #clear per (key_name, key)     ruby.rb:15-35, 57-63
  *   bf_optimal_m/_k    Redis::Bloomfilter.optimal_m / optimal_k       lib/redis/bloomfilter.rb:50-58
  *   bf_version         Redis::Bloomfilter.version                     lib/redis/bloomfilter/version.rb:6-8
  *
@@ -605,6 +607,96 @@ int  bf_lua_export_layer(bf_lua* h, uint32_t layer, uint8_t* buf, uint64_t cap, 
 int  bf_lua_import_layer(bf_lua* h, uint32_t layer, const uint8_t* buf, uint64_t len);
 int  bf_lua_layer_params(double entries, double precision, uint32_t layer, uint64_t* bits, uint32_t* k);
 int  bf_lua_index(double entries, uint64_t count, uint32_t* layer);
+
+/* ---- filter banks: n_filters filters of identical (m_bits, k) behind one handle.  In the
+ *      reference `key_name` names a filter (lib/redis/bloomfilter.rb:30, ruby.rb:33-35, 59) and an
+ *      application keeps one per tenant, per day or per feed, all built with the same size and
+ *      error_rate.  A bank holds them in ONE device allocation and takes a mixed batch of
+ *      (filter id, key) pairs in one launch.
+ *
+ *      Layout: filter f is a Redis string in SETBIT byte order (ruby.rb:59), exactly as a
+ *      bf_handle holds one, starting at byte f * stride; stride = ceil(m_bits / 8) rounded up to
+ *      128 bytes (bf_bank_stride).  The bytes from ceil(m_bits / 8) to stride are always zero.
+ *      Offsets are the ruby derivation (ruby.rb:41-55); there are no hash engines, shards or
+ *      multi-device banks.  A bank has its own error string, mutex and stream: calls on one bank
+ *      are ordered (across streams too, as on a bf_handle), the *_dev forms take device pointers
+ *      and a hipStream_t and do not synchronise; different banks and handles are independent.
+ *
+ *   bf_bank_create       Redis::Bloomfilter#initialize, once per key_name   lib/redis/bloomfilter.rb:17-46
+ *                        (m = options[:bits], k = options[:hashes], bloomfilter.rb:27-28); cfg: only
+ *                        device, batch_keys and batch_bytes are used; shard_count > 1, device_count
+ *                        > 0 and any flag (BF_FLAG_ENGINE_*, BF_FLAG_ENCODER, ...) are BF_EINVAL.
+ *                        NULL out, m_bits == 0, k == 0, k > BF_MAX_K, n_filters == 0 or > 2^32 and a
+ *                        byte size n_filters * stride that overflows 64 bits are BF_EINVAL before
+ *                        any device call.
+ *   bf_bank_destroy      (the driver objects going out of scope)
+ *   bf_bank_last_error   b == NULL: last error of bf_bank_create on this thread
+ *   bf_bank_info         m, k, n_filters, stride and the allocation's bytes (each nullable)
+ *   bf_bank_stride       the stride of a filter of m_bits (host only)
+ *   bf_bank_stream       the bank's own (non-blocking) hipStream_t
+ *   bf_bank_sync         synchronise the bank's stream and the stream of its last call.  The ONE
+ *                        place that reports what the kernels of *_dev calls skipped (below): then
+ *                        BF_EINVAL, once; a later call still runs.
+ *   bf_bank_insert_many  Ruby#insert of key j into the filter named filter_ids[j]   ruby.rb:15-17, 57-63
+ *                        key_flipped (nullable, n bytes): 1 iff this key's own atomic turned at
+ *                        least one bit 0 -> 1 in this call.  When several keys of the batch race
+ *                        for one bit exactly one of them reports it, so the OR of key_flipped
+ *                        over a filter's keys is exactly "this filter's string changed": the
+ *                        reference's !found (ruby.rb:61-62), which drives EXPIRE per key_name.
+ *                        Per key it is NOT the sequential flag (which key of several wins a bit is
+ *                        unspecified; bf_insert_many's per_key_new has no counterpart here).
+ *   bf_bank_include_many Ruby#include? of key j in filter filter_ids[j]: out[j] = 0 / 1   ruby.rb:20-30
+ *   bf_bank_clear        Ruby#clear (DEL key_name) of the listed filters   ruby.rb:33-35
+ *                        ids == NULL: every filter (count is not read).
+ *   bf_bank_bitcount     BITCOUNT key_name of the count listed filters in one launch, out[i]
+ *                        64-bit (ruby.rb:59, the SETBIT layout); ids == NULL: every filter in
+ *                        order, count must be n_filters.
+ *   bf_bank_export_filters  GET key_name of the listed filters: filter ids[i]'s stride bytes at
+ *                        buf + i * stride (count * stride bytes in all) and its trimmed Redis
+ *                        length (last non-zero byte + 1, 0 for an empty filter: the length the
+ *                        SETBITs of ruby.rb:59 grow the key to) in lens[i].  ids == NULL as above.
+ *   bf_bank_import_filters  SET key_name of the listed filters (ids should be distinct): the
+ *                        first lens[i] bytes at buf + i * stride replace filter ids[i]
+ *                        (BF_IMPORT_REPLACE, zero-filled past lens[i]) or are ORed into it
+ *                        (BF_IMPORT_OR).  A string bf_import_redis would refuse (longer than
+ *                        ceil(m / 8) bytes, or a bit set at or past m) is BF_ERANGE, as there, and
+ *                        nothing is imported.
+ *
+ *      Refusals.  The host-pointer forms check first: bf_check_offsets' rule on the offsets and
+ *      every filter id < n_filters; on failure nothing is launched, the call returns BF_EINVAL
+ *      and bf_bank_last_error names the first bad key (or list entry).  The *_dev forms cannot
+ *      read their inputs, so the kernels guard every lane: a key whose filter id is out of range
+ *      or whose offsets fail the rule is SKIPPED (it sets no bit, answers 0 and reports
+ *      key_flipped 0; it is not hashed as the empty string), a listed filter out of range is left
+ *      alone (its BITCOUNT reads 0), and the bank's status word is set for bf_bank_sync.
+ *      Device key bytes need bf_insert_many_dev's 16 readable bytes past d_offsets[n]. */
+typedef struct bf_bank bf_bank;
+int  bf_bank_create(uint64_t m_bits, uint32_t k, uint64_t n_filters, const bf_config* cfg, bf_bank** out);
+int  bf_bank_destroy(bf_bank* b);
+const char* bf_bank_last_error(const bf_bank* b);
+int  bf_bank_info(const bf_bank* b, uint64_t* m_bits, uint32_t* k, uint64_t* n_filters, uint64_t* stride,
+                  uint64_t* device_bytes);
+int  bf_bank_stride(uint64_t m_bits, uint64_t* stride);
+int  bf_bank_stream(bf_bank* b, void** stream);
+int  bf_bank_sync(bf_bank* b);
+int  bf_bank_insert_many(bf_bank* b, const uint8_t* key_bytes, const uint64_t* offsets, const uint32_t* filter_ids,
+                         uint64_t n, uint8_t* key_flipped /* nullable, n bytes */);
+int  bf_bank_insert_many_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets,
+                             const uint32_t* d_filter_ids, uint64_t n, uint8_t* d_key_flipped /* nullable */,
+                             void* stream);
+int  bf_bank_include_many(bf_bank* b, const uint8_t* key_bytes, const uint64_t* offsets, const uint32_t* filter_ids,
+                          uint64_t n, uint8_t* out /* n bytes, 0/1 */);
+int  bf_bank_include_many_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets,
+                              const uint32_t* d_filter_ids, uint64_t n, uint8_t* d_out, void* stream);
+int  bf_bank_clear(bf_bank* b, const uint32_t* ids /* nullable: all */, uint64_t count);
+int  bf_bank_clear_dev(bf_bank* b, const uint32_t* d_ids /* nullable: all */, uint64_t count, void* stream);
+int  bf_bank_bitcount(bf_bank* b, const uint32_t* ids /* nullable: all */, uint64_t count, uint64_t* out);
+int  bf_bank_bitcount_dev(bf_bank* b, const uint32_t* d_ids /* nullable: all */, uint64_t count, uint64_t* d_out,
+                          void* stream);
+int  bf_bank_export_filters(bf_bank* b, const uint32_t* ids /* nullable: all */, uint64_t count,
+                            uint8_t* buf /* count * stride bytes */, uint64_t* lens /* count */);
+int  bf_bank_import_filters(bf_bank* b, const uint32_t* ids /* nullable: all */, uint64_t count, const uint8_t* buf,
+                            const uint64_t* lens, uint32_t mode /* BF_IMPORT_* */);
 
 /* ---- one key's k offsets without a filter (Ruby#indexes_for, ruby.rb:41-55): computed
  *      by the same device kernel as bf_indexes_many, on the calling thread's current

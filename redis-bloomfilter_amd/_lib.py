@@ -157,6 +157,23 @@ SIGNATURES = {
     "bf_lua_import_layer": (ctypes.c_int, [_vp, _u32, _vp, _u64]),
     "bf_lua_layer_params": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, _u32, _u64p, _u32p]),
     "bf_lua_index": (ctypes.c_int, [ctypes.c_double, _u64, _u32p]),
+    "bf_bank_create": (ctypes.c_int, [_u64, _u32, _u64, ctypes.POINTER(bf_config), ctypes.POINTER(_vp)]),
+    "bf_bank_destroy": (ctypes.c_int, [_vp]),
+    "bf_bank_last_error": (ctypes.c_char_p, [_vp]),
+    "bf_bank_info": (ctypes.c_int, [_vp, _u64p, _u32p, _u64p, _u64p, _u64p]),
+    "bf_bank_stride": (ctypes.c_int, [_u64, _u64p]),
+    "bf_bank_stream": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
+    "bf_bank_sync": (ctypes.c_int, [_vp]),
+    "bf_bank_insert_many": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
+    "bf_bank_insert_many_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "bf_bank_include_many": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
+    "bf_bank_include_many_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "bf_bank_clear": (ctypes.c_int, [_vp, _vp, _u64]),
+    "bf_bank_clear_dev": (ctypes.c_int, [_vp, _vp, _u64, _vp]),
+    "bf_bank_bitcount": (ctypes.c_int, [_vp, _vp, _u64, _vp]),
+    "bf_bank_bitcount_dev": (ctypes.c_int, [_vp, _vp, _u64, _vp, _vp]),
+    "bf_bank_export_filters": (ctypes.c_int, [_vp, _vp, _u64, _vp, _vp]),
+    "bf_bank_import_filters": (ctypes.c_int, [_vp, _vp, _u64, _vp, _vp, _u32]),
     "bf_optimal_m": (ctypes.c_int64, [ctypes.c_double, ctypes.c_double]),
     "bf_optimal_k": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
 }
@@ -771,6 +788,192 @@ class Filter:
         buf = np.frombuffer(data, np.uint8) if len(data) else np.zeros(1, np.uint8)
         _check(self._lib.bf_shard_import(self.handle, _ptr(buf), len(buf) if len(data) else 0, int(mode)),
                self._h)
+
+
+def bank_stride(m_bits: int) -> int:
+    """Bytes between two filters of a bank: ceil(m_bits / 8) rounded up to 128 (bf_bank_stride)."""
+    out = ctypes.c_uint64()
+    if not 0 <= int(m_bits) < 1 << 64 or load().bf_bank_stride(int(m_bits), ctypes.byref(out)):
+        raise ArgumentError("bf_bank_stride(%r): m_bits must be positive and its stride fit 64 bits" % (m_bits,))
+    return int(out.value)
+
+
+def _bank_check(code: int, h=None) -> None:
+    if code == BF_OK:
+        return
+    msg = load().bf_bank_last_error(h).decode(errors="replace")
+    if code in (BF_EINVAL, BF_ERANGE):
+        raise ArgumentError("%s: %s" % (_STATUS.get(code), msg))
+    raise BfHipError(code, msg)
+
+
+class FilterBank:
+    """``n_filters`` device-resident filters of one (m_bits, k) behind one handle (a ``bf_bank*``;
+    see include/bfhip.h).  Filter ``f`` is a Redis string in SETBIT order at byte ``f * stride``
+    of one allocation; a batch names each key's filter in ``filter_ids`` (uint32).
+
+    Arrays are numpy as for ``Filter``; the ``*_dev`` methods take raw device addresses (ints)
+    and a hipStream_t as an int (``stream=None``: the bank's own stream, ``0``: the null stream)
+    and do not synchronise.  ``ids=None`` lists every filter in order."""
+
+    def __init__(self, m_bits: int, k: int, n_filters: int, device: int = -1, batch_keys: int = 0,
+                 batch_bytes: int = 0):
+        self._lib = load()
+        for what, v in (("m_bits", m_bits), ("n_filters", n_filters)):
+            if not 0 <= int(v) < 1 << 64:
+                raise ArgumentError("%s must be an unsigned 64-bit integer, got %r" % (what, v))
+        if not 0 <= int(k) < 1 << 32:
+            raise ArgumentError("k must be in [1, %d], got %r" % (BF_MAX_K, k))
+        cfg = bf_config(ctypes.sizeof(bf_config), int(device), int(batch_keys), int(batch_bytes), 1, 0, 0, 0)
+        h = _vp()
+        _bank_check(self._lib.bf_bank_create(int(m_bits), int(k), int(n_filters), ctypes.byref(cfg), ctypes.byref(h)))
+        self._h = h
+        m, kk = ctypes.c_uint64(), ctypes.c_uint32()
+        nf, st, db = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _bank_check(self._lib.bf_bank_info(h, ctypes.byref(m), ctypes.byref(kk), ctypes.byref(nf), ctypes.byref(st),
+                                           ctypes.byref(db)), h)
+        self.m, self.k, self.n_filters, self.stride, self.device_bytes = m.value, kk.value, nf.value, st.value, db.value
+        self.device = int(device)
+
+    # -- lifecycle
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.bf_bank_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise ArgumentError("bank is closed")
+        return self._h
+
+    def sync(self) -> None:
+        """Wait for the bank's work; ArgumentError (once) when a ``*_dev`` call's kernel skipped
+        a key or a listed filter (an id out of range, inconsistent key offsets)."""
+        _bank_check(self._lib.bf_bank_sync(self.handle), self._h)
+
+    def _s(self, stream):
+        if stream is None:
+            if getattr(self, "_own_stream", None) is None:
+                p = _vp()
+                _bank_check(self._lib.bf_bank_stream(self.handle, ctypes.byref(p)), self._h)
+                self._own_stream = p.value or 0
+            return self._own_stream or None
+        return int(stream) or None
+
+    # -- host-pointer batch API
+    @staticmethod
+    def _batch(keys, offsets, filter_ids):
+        keys, offsets, n = Filter._keys(keys, offsets)
+        ids = np.ascontiguousarray(filter_ids)
+        if ids.ndim != 1 or len(ids) != n:
+            raise ArgumentError("filter_ids must be a 1-D array of n entries")
+        if n and (ids.dtype.kind not in "iu" or int(ids.min()) < 0 or int(ids.max()) > 0xFFFFFFFF):
+            raise ArgumentError("filter_ids must be unsigned 32-bit integers")
+        ids = ids.astype(np.uint32, copy=False) if n else np.zeros(1, np.uint32)
+        return keys, offsets, ids, n
+
+    def insert_many(self, keys: np.ndarray, offsets: np.ndarray, filter_ids: np.ndarray,
+                    key_flipped: bool = True) -> Optional[np.ndarray]:
+        """Key j goes into filter filter_ids[j].  Returns the per-key flags (uint8: this key's own
+        atomic flipped a bit; OR them per filter for "this filter's string changed"), or None
+        with ``key_flipped=False``."""
+        keys, offsets, ids, n = self._batch(keys, offsets, filter_ids)
+        kf = np.zeros(max(n, 1), np.uint8) if key_flipped else None
+        _bank_check(self._lib.bf_bank_insert_many(self.handle, _ptr(keys), _ptr(offsets), _ptr(ids), n, _ptr(kf)),
+                    self._h)
+        return kf[:n] if key_flipped else None
+
+    def include_many(self, keys: np.ndarray, offsets: np.ndarray, filter_ids: np.ndarray) -> np.ndarray:
+        keys, offsets, ids, n = self._batch(keys, offsets, filter_ids)
+        out = np.zeros(max(n, 1), np.uint8)
+        _bank_check(self._lib.bf_bank_include_many(self.handle, _ptr(keys), _ptr(offsets), _ptr(ids), n, _ptr(out)),
+                    self._h)
+        return out[:n]
+
+    def _ids(self, ids):
+        """(uint32 array or None, count) of an id list; None lists every filter."""
+        if ids is None:
+            return None, self.n_filters
+        a = np.ascontiguousarray(ids)
+        if a.ndim != 1:
+            raise ArgumentError("ids must be a 1-D array")
+        if len(a) and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise ArgumentError("ids must be unsigned 32-bit integers")
+        return (a.astype(np.uint32, copy=False) if len(a) else np.zeros(1, np.uint32)), len(a)
+
+    def clear(self, ids=None) -> None:
+        a, count = self._ids(ids)
+        _bank_check(self._lib.bf_bank_clear(self.handle, _ptr(a), count), self._h)
+
+    def bitcount(self, ids=None) -> np.ndarray:
+        """BITCOUNT of every listed filter (uint64), one launch."""
+        a, count = self._ids(ids)
+        out = np.zeros(max(count, 1), np.uint64)
+        _bank_check(self._lib.bf_bank_bitcount(self.handle, _ptr(a), count, _ptr(out)), self._h)
+        return out[:count]
+
+    def export_filters(self, ids=None) -> Tuple[np.ndarray, np.ndarray]:
+        """(buf, lens): buf[i] holds the stride bytes of listed filter i (a (count, stride) uint8
+        array), lens[i] its trimmed Redis length."""
+        a, count = self._ids(ids)
+        buf = np.zeros((max(count, 1), self.stride), np.uint8)
+        lens = np.zeros(max(count, 1), np.uint64)
+        _bank_check(self._lib.bf_bank_export_filters(self.handle, _ptr(a), count, _ptr(buf), _ptr(lens)), self._h)
+        return buf[:count], lens[:count]
+
+    def export_redis(self, ids=None) -> List[bytes]:
+        """The trimmed Redis string of every listed filter (b"" for an empty one)."""
+        buf, lens = self.export_filters(ids)
+        return [buf[i, : int(lens[i])].tobytes() for i in range(len(lens))]
+
+    def import_redis(self, ids, strings, mode: int = BF_IMPORT_REPLACE) -> None:
+        """Load one Redis string per listed filter (bf_bank_import_filters); ArgumentError and
+        nothing imported when one is longer than ceil(m / 8) or sets a bit at or past m."""
+        a, count = self._ids(ids)
+        strings = list(strings)
+        if len(strings) != count:
+            raise ArgumentError("%d strings for %d filters" % (len(strings), count))
+        lens = np.array([len(s) for s in strings] or [0], np.uint64)
+        buf = np.zeros((max(count, 1), self.stride), np.uint8)
+        for i, s in enumerate(strings):
+            ln = min(len(s), self.stride)   # a longer string is refused by its length
+            buf[i, :ln] = np.frombuffer(bytes(s[:ln]), np.uint8)
+        _bank_check(self._lib.bf_bank_import_filters(self.handle, _ptr(a), count, _ptr(buf), _ptr(lens), int(mode)),
+                    self._h)
+
+    # -- device-resident API
+    def insert_many_dev(self, d_keys: int, d_offsets: int, d_filter_ids: int, n: int, d_key_flipped: int = 0,
+                        stream=None) -> None:
+        _bank_check(self._lib.bf_bank_insert_many_dev(self.handle, d_keys, d_offsets, d_filter_ids, int(n),
+                                                      d_key_flipped or None, self._s(stream)), self._h)
+
+    def include_many_dev(self, d_keys: int, d_offsets: int, d_filter_ids: int, n: int, d_out: int,
+                         stream=None) -> None:
+        _bank_check(self._lib.bf_bank_include_many_dev(self.handle, d_keys, d_offsets, d_filter_ids, int(n), d_out,
+                                                       self._s(stream)), self._h)
+
+    def clear_dev(self, d_ids: int = 0, count: int = 0, stream=None) -> None:
+        _bank_check(self._lib.bf_bank_clear_dev(self.handle, d_ids or None, int(count), self._s(stream)), self._h)
+
+    def bitcount_dev(self, d_out: int, d_ids: int = 0, count: Optional[int] = None, stream=None) -> None:
+        """Per-filter BITCOUNT on ``stream``; ``count`` uint64 are written at d_out (d_ids = 0:
+        every filter, count = n_filters)."""
+        count = self.n_filters if count is None else int(count)
+        _bank_check(self._lib.bf_bank_bitcount_dev(self.handle, d_ids or None, count, d_out, self._s(stream)),
+                    self._h)
 
 
 def lua_layer_params(entries, precision, layer: int) -> Tuple[int, int]:

@@ -1,0 +1,229 @@
+"""``BloomfilterBank`` — many ``Redis::Bloomfilter`` key names of one size and error rate on
+one device allocation (a ``bf_bank``, include/bfhip.h).
+
+In the reference ``key_name`` names a filter (lib/redis/bloomfilter.rb:14, ruby.rb:33-35, 59)
+and an application keeps one per tenant, per day or per feed.  A bank fixes the list of key
+names at construction (``key_names[i]`` is filter ``i``), sizes every filter with
+``Bloomfilter.optimal_m`` / ``optimal_k`` (bloomfilter.rb:25-28) and takes a mixed batch of
+``(key name, key)`` pairs in one launch.
+
+Redis sync follows ``drivers/hip.py``'s contract, per key name:
+
+* attach (``redis=``): every key name that exists is imported (a filter written by the ruby
+  driver is readable here) and its PTTL mirrored;
+* ``sync='write_through'`` (default): after an insert each key name whose string CHANGED is
+  written back, its trimmed string with ``SETRANGE name 0`` (keeps the TTL; under OR a string
+  only grows, so the key becomes exactly the string the ruby driver's SETBITs build), followed
+  by EXPIRE when ``expire`` is given — ruby.rb:61-62, per key name;
+* ``sync='manual'``: Redis is touched only by ``flush`` / ``reload`` / ``clear``;
+* TTL: when a key name's mirrored deadline passes, that one filter is cleared, as the Redis key
+  would have vanished.
+"""
+from __future__ import annotations
+
+import time
+from typing import Dict, Iterable, List, Optional, Sequence, Set
+
+import numpy as np
+
+from . import fakeredis
+from . import keys as _keys
+from ._lib import ArgumentError, BF_IMPORT_REPLACE, FilterBank, estimate_count
+from .bloomfilter import Bloomfilter
+
+
+class BankFilter:
+    """``bank[name]``: the reference's ``insert`` / ``include`` / ``clear`` for one key name."""
+
+    def __init__(self, bank: "BloomfilterBank", name: str):
+        self.bank, self.key_name = bank, name
+
+    def insert(self, data, expire=None):
+        return self.bank.insert(self.key_name, data, expire)
+
+    def include(self, key) -> bool:
+        return self.bank.include(self.key_name, key)
+
+    __contains__ = include
+
+    def clear(self):
+        return self.bank.clear(self.key_name)
+
+
+class BloomfilterBank:
+    SYNC_MODES = ("write_through", "manual")
+
+    def __init__(self, size=None, error_rate=None, key_names: Optional[Sequence] = None, redis=None,
+                 sync: str = "write_through", default_expire=None, device: int = -1, clock=time.monotonic):
+        # bloomfilter.rb:21
+        if error_rate is None or size is None:
+            raise ArgumentError("options[:size] && options[:error_rate] cannot be nil")
+        names = [str(n) for n in (key_names or [])]
+        if not names:
+            raise ArgumentError("key_names must list at least one key name")
+        if len(set(names)) != len(names):
+            dup = sorted(n for n in set(names) if names.count(n) > 1)
+            raise ArgumentError("key_names repeats %r" % dup[0])
+        if sync not in self.SYNC_MODES:
+            raise ArgumentError("sync must be one of %s" % (self.SYNC_MODES,))
+        self.options = {"size": size, "error_rate": error_rate, "default_expire": default_expire,
+                        "bits": Bloomfilter.optimal_m(size, error_rate)}
+        self.options["hashes"] = Bloomfilter.optimal_k(size, self.options["bits"])   # bloomfilter.rb:25-28
+        if self.options["bits"] <= 0:
+            raise ArgumentError("filter size in bits must be positive (got %r)" % (self.options["bits"],))
+        self.key_names: List[str] = names
+        self.ids: Dict[str, int] = {n: i for i, n in enumerate(names)}
+        self.sync_mode = sync
+        self._clock = clock
+        self.bank = FilterBank(self.options["bits"], self.options["hashes"], len(names), device=device)
+        self._deadline: Dict[int, float] = {}
+        self._dirty: Set[int] = set()    # manual sync: filters changed since the last flush
+        self.redis = redis if redis is not None else fakeredis.current()   # bloomfilter.rb:30
+        self.reload()
+
+    # -- helpers
+    def _id(self, name) -> int:
+        try:
+            return self.ids[str(name)]
+        except KeyError:
+            raise ArgumentError("unknown key name %r" % (name,)) from None
+
+    def _expire(self, expire):
+        """``expire || @options[:default_expire]`` (bloomfilter.rb:62)."""
+        return self.options["default_expire"] if expire is None or expire is False else expire
+
+    def _batch(self, names, keys):
+        names, keys = list(names), list(keys)
+        if len(names) != len(keys):
+            raise ArgumentError("%d key names for %d keys" % (len(names), len(keys)))
+        ids = np.array([self._id(n) for n in names], np.uint32)
+        buf, offs = _keys.pack(keys)
+        return ids, buf, offs
+
+    def _expired(self) -> None:
+        """Clear every filter whose mirrored deadline has passed (and DEL it, write-through)."""
+        if not self._deadline:
+            return
+        now = self._clock()
+        due = [i for i, t in self._deadline.items() if now >= t]
+        if not due:
+            return
+        self.bank.clear(np.array(due, np.uint32))
+        for i in due:
+            del self._deadline[i]
+            self._dirty.discard(i)
+            if self.redis is not None and self.sync_mode == "write_through":
+                self.redis.delete(self.key_names[i])
+
+    def _write(self, ids: Sequence[int]) -> int:
+        """SETRANGE name 0 <trimmed string> for every listed filter; returns the bytes sent."""
+        ids = sorted(ids)
+        if not ids or self.redis is None:
+            return 0
+        sent = 0
+        for i, s in zip(ids, self.bank.export_redis(np.array(ids, np.uint32))):
+            if s:
+                self.redis.setrange(self.key_names[i], 0, s)
+                sent += len(s)
+        return sent
+
+    # -- ruby.rb:15-17 / 57-63, per key name
+    def insert_many(self, names: Iterable, keys: Iterable, expire=None) -> Set[str]:
+        """Key j goes into the filter named names[j].  Returns the set of key names whose string
+        changed (the reference's ``!found`` per key name)."""
+        self._expired()
+        ids, buf, offs = self._batch(names, keys)
+        flipped = self.bank.insert_many(buf, offs, ids)
+        changed = sorted(set(ids[flipped != 0].tolist()))
+        expire = self._expire(expire)
+        armed = expire is not None and expire is not False   # ruby.rb:62: 0 counts
+        write = self.redis is not None and self.sync_mode == "write_through"
+        if write:
+            self._write(changed)
+        else:
+            self._dirty.update(changed)
+        if armed:
+            t0 = self._clock()
+            for i in changed:
+                self._deadline[i] = t0 + float(expire)
+                if write:
+                    self.redis.expire(self.key_names[i], expire)
+        return {self.key_names[i] for i in changed}
+
+    def insert(self, name, key, expire=None) -> bool:
+        return bool(self.insert_many([name], [key], expire))
+
+    # -- ruby.rb:20-30
+    def include_many(self, names: Iterable, keys: Iterable) -> np.ndarray:
+        self._expired()
+        ids, buf, offs = self._batch(names, keys)
+        return self.bank.include_many(buf, offs, ids).astype(bool)
+
+    def include(self, name, key) -> bool:
+        return bool(self.include_many([name], [key])[0])
+
+    # -- ruby.rb:33-35
+    def clear(self, name=None) -> None:
+        """DEL one key name's filter, or every one (``name=None``)."""
+        ids = list(range(len(self.key_names))) if name is None else [self._id(name)]
+        self.bank.clear(None if name is None else np.array(ids, np.uint32))
+        for i in ids:
+            self._deadline.pop(i, None)
+            self._dirty.discard(i)
+        if self.redis is not None:
+            self.redis.delete(*[self.key_names[i] for i in ids])
+
+    def __getitem__(self, name) -> BankFilter:
+        self._id(name)
+        return BankFilter(self, str(name))
+
+    # -- statistics
+    def count_bits(self) -> np.ndarray:
+        """BITCOUNT of every key name, in ``key_names`` order, counted on the device."""
+        self._expired()
+        return self.bank.bitcount()
+
+    def estimated_sizes(self) -> np.ndarray:
+        """About how many distinct keys each filter holds (``estimate_count`` of its bit count)."""
+        m, k = self.options["bits"], self.options["hashes"]
+        return np.array([estimate_count(m, k, int(x)) for x in self.count_bits()], np.float64)
+
+    # -- Redis sync
+    def flush(self, full: bool = False) -> int:
+        """Write the filters that changed since the last flush (``full``: every non-empty one)."""
+        self._expired()
+        ids = range(len(self.key_names)) if full else self._dirty
+        sent = self._write(list(ids))
+        if self.redis is not None:
+            self._dirty.clear()
+        return sent
+
+    def reload(self, names: Optional[Iterable] = None) -> None:
+        """Replace the listed filters (default: all) with their Redis keys' current values."""
+        if self.redis is None:
+            return
+        ids = list(range(len(self.key_names))) if names is None else [self._id(n) for n in names]
+        have, strings, gone = [], [], []
+        for i in ids:
+            t0 = self._clock()
+            data = self.redis.get(self.key_names[i])
+            self._deadline.pop(i, None)
+            self._dirty.discard(i)
+            if data is None:
+                gone.append(i)
+                continue
+            have.append(i)
+            strings.append(bytes(data))
+            ttl = self.redis.pttl(self.key_names[i]) if hasattr(self.redis, "pttl") else -1
+            if ttl is not None and ttl > 0:
+                self._deadline[i] = t0 + ttl / 1000.0
+        if gone:
+            self.bank.clear(np.array(gone, np.uint32))
+        if have:
+            self.bank.import_redis(np.array(have, np.uint32), strings, BF_IMPORT_REPLACE)
+
+    def to_redis_string(self, name) -> bytes:
+        return self.bank.export_redis(np.array([self._id(name)], np.uint32))[0]
+
+    def close(self) -> None:
+        self.bank.close()

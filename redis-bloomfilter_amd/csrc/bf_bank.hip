@@ -1,0 +1,829 @@
+// bf_bank.hip — a filter bank: n_filters Bloom filters of identical (m, k) behind one handle
+// (include/bfhip.h, bf_bank_*).  In the reference `key_name` names a filter
+// (lib/redis/bloomfilter.rb:30) and an application keeps one per tenant, per day or per feed;
+// here they share one device allocation and a mixed batch of (filter id, key) pairs is one
+// launch.
+//
+// Layout: filter f is the Redis string SETBIT builds (ruby.rb:59), exactly as a bf_handle holds
+// one, at byte f * stride of the allocation; stride = ceil(m / 8) rounded up to 128 bytes, so
+// every filter starts on a cache line and no 32-bit word straddles two filters.  The bytes
+// from ceil(m / 8) to stride stay zero.  Every address is formed in 64 bits: n_filters * stride
+// may exceed 4 GiB.
+//
+// Kernels:
+//   bank_keys_kernel    insert / include?: one lane per key, 256 keys per workgroup staged
+//                       through LDS (bfdev::for_key_tile), SHA-1 and the offsets of ruby.rb:41-55
+//                       from bf_device.h, the k probes inside the lane's own filter.
+//   bank_*_kernel       per-filter BITCOUNT, clear, gather-and-trim (export) and scatter
+//                       (import): a workgroup, or a wave when stride <= kWaveStrideBytes, owns
+//                       one listed filter, streams it in 16-byte vectors and reduces with
+//                       shuffles; one writer per output, no global atomics.
+#include "bfhip.h"
+#include "bf_device.h"
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+using namespace bfdev;
+
+namespace {
+
+constexpr int kBankTile = 256;                 // lanes = keys per workgroup of the keyed kernel
+constexpr int kBankStageVec = kStageBytes / 16;
+constexpr uint32_t kBankLanes = 256;           // lanes per workgroup of the per-filter kernels
+constexpr uint32_t kWaveStrideBytes = 4096;    // a filter this small is owned by one wave (<= 4 vectors per lane)
+constexpr uint32_t kBankMaxBlocks = 1u << 16;  // per-filter kernels: the grid strides beyond this
+
+thread_local std::string g_bank_create_error;
+
+enum : int { BANK_INSERT = 0, BANK_INCLUDE = 1 };
+
+// status[0]: a key's offsets failed bfdev::key_ok; status[1]: a filter id >= n_filters.
+// Both live in the bank's pinned status block, which bf_bank_sync reports.
+template <int OP>
+__global__ __launch_bounds__(kBankTile) void bank_keys_kernel(BfGeom g, uint64_t n_filters, uint64_t stride_words,
+                                                              const uint8_t* __restrict__ keys16,
+                                                              const uint64_t* __restrict__ offsets, uint64_t bias,
+                                                              const uint32_t* __restrict__ ids, uint64_t n,
+                                                              uint8_t* __restrict__ out8,
+                                                              uint32_t* __restrict__ status) {
+    __shared__ uint64_t s_off[kBankTile + 1];
+    __shared__ uint4 s_stage[kBankStageVec + kStageSlackVec];
+    const uint64_t tile0 = (uint64_t)blockIdx.x * kBankTile;
+    const uint32_t cnt = (uint32_t)((n - tile0) < (uint64_t)kBankTile ? (n - tile0) : kBankTile);
+    for_key_tile<kBankTile, kBankStageVec>(keys16, offsets, bias, tile0, cnt, s_off, s_stage, status,
+        [&](auto staged, uint32_t lane, const uint32_t* src, uint32_t s, uint32_t L) {
+            const uint64_t j = tile0 + lane;
+            const uint32_t id = ids[j];
+            // for_key_tile hands a refused key over as the empty key: tell the two apart again.
+            // Every lane hashes (the staged SHA-1 reduces over the wave), a skipped lane drops
+            // out after it: no bit set, answer 0, key_flipped 0.
+            bool ok = key_ok(s_off[0], s_off[lane], s_off[lane + 1], s_off[cnt], nullptr);
+            if ((uint64_t)id >= n_filters) {
+                status[1] = 1u;
+                ok = false;
+            }
+            uint32_t H[5];
+            sha1_any<decltype(staged)::value>(src, s, L, H);
+            if (!ok) {
+                if (out8) out8[j] = 0;
+                return;
+            }
+            uint32_t* __restrict__ fb = g.bits + (uint64_t)id * stride_words;   // 64-bit word index
+            const uint32_t k = g.k;
+            if constexpr (OP == BANK_INCLUDE) {
+                // every load of a round is issued before any is used; a lane whose AND already
+                // failed stops after its round (ruby.rb:23's early exit)
+                uint32_t hit = 1u;
+                for (uint32_t i0 = 0; i0 < k && (hit & 1u); i0 += kChunk) {
+                    uint32_t v[kChunk], sh[kChunk];
+#pragma unroll
+                    for (int c = 0; c < kChunk; ++c) {
+                        v[c] = 0xFFFFFFFFu; sh[c] = 0;
+                        if (i0 + c < k) {
+                            const uint64_t o = probe_offset(g, H[0], H[1], H[2], H[3], i0 + c);
+                            sh[c] = (uint32_t)(o ^ 7u) & 31u;
+                            v[c] = fb[o >> 5];
+                        }
+                    }
+#pragma unroll
+                    for (int c = 0; c < kChunk; ++c) hit &= v[c] >> sh[c];
+                }
+                out8[j] = (uint8_t)(hit & 1u);
+            } else {
+                // test-then-set (the insert_test policy of bf_kernels.hip): a 1 seen by the load
+                // is final, a stale 0 costs an atomic whose return value tells the truth.  The
+                // atomic's old value decides "flipped": of several lanes racing for one bit
+                // exactly one sees it unset.
+                uint32_t flipped = 0;
+                for (uint32_t i0 = 0; i0 < k; i0 += kChunk) {
+                    uint32_t w[kChunk], mask[kChunk], v[kChunk];
+#pragma unroll
+                    for (int c = 0; c < kChunk; ++c) {
+                        w[c] = 0; mask[c] = 0; v[c] = 0;
+                        if (i0 + c < k) {
+                            const uint64_t o = probe_offset(g, H[0], H[1], H[2], H[3], i0 + c);
+                            w[c] = (uint32_t)(o >> 5);   // < stride_words <= 2^32 (checked at create)
+                            mask[c] = 1u << ((uint32_t)(o ^ 7u) & 31u);
+                            v[c] = fb[w[c]];
+                        }
+                    }
+#pragma unroll
+                    for (int c = 0; c < kChunk; ++c) {
+                        if (mask[c] && !(v[c] & mask[c])) {
+                            const uint32_t old = __hip_atomic_fetch_or(fb + w[c], mask[c], __ATOMIC_RELAXED,
+                                                                       __HIP_MEMORY_SCOPE_AGENT);
+                            flipped |= (old & mask[c]) ? 0u : 1u;
+                        }
+                    }
+                }
+                if (out8) out8[j] = (uint8_t)flipped;
+            }
+        });
+}
+
+// ---- per-filter kernels -------------------------------------------------------------------
+
+__device__ __forceinline__ uint32_t popc4(const uint4& v) {
+    return __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
+}
+
+// 1 + the index of the last non-zero byte of a vector (device byte b is bits 8 (b & 3).. of
+// word b >> 2), 0 for a zero vector.
+__device__ __forceinline__ uint32_t last_byte(const uint4& v) {
+    if (v.w) return 16u - ((uint32_t)__builtin_clz(v.w) >> 3);
+    if (v.z) return 12u - ((uint32_t)__builtin_clz(v.z) >> 3);
+    if (v.y) return 8u - ((uint32_t)__builtin_clz(v.y) >> 3);
+    if (v.x) return 4u - ((uint32_t)__builtin_clz(v.x) >> 3);
+    return 0u;
+}
+
+// The first `nbytes` (0..16) bytes of a vector, the rest zeroed.
+__device__ __forceinline__ uint4 keep_bytes(uint4 v, uint32_t nbytes) {
+    uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) {
+        const uint32_t nb = nbytes > 4 * i ? (nbytes - 4 * i < 4 ? nbytes - 4 * i : 4u) : 0u;
+        w[i] &= nb == 4 ? 0xFFFFFFFFu : ((1u << (8 * nb)) - 1u);
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// Who owns which listed filter: by stride (a kernel argument, so the choice is
+// workgroup-uniform) either each wave of the workgroup one item or the whole workgroup one.
+struct Owner {
+    bool wave;        // a wave owns an item
+    uint32_t lane;    // this lane's index among the owner's lanes
+    uint32_t lanes;   // lanes of the owner
+};
+
+__device__ __forceinline__ Owner bank_owner(uint64_t stride_vec) {
+    Owner o;
+    o.wave = stride_vec * 16 <= kWaveStrideBytes;
+    o.lane = o.wave ? (threadIdx.x & 63u) : threadIdx.x;
+    o.lanes = o.wave ? 64u : kBankLanes;
+    return o;
+}
+
+// Sum / max over the owner's lanes, returned to every one of them.  Workgroup owners go
+// through LDS with two barriers (every lane of the workgroup calls this together).
+template <bool MAX>
+__device__ __forceinline__ unsigned long long owner_reduce(unsigned long long v, const Owner& o,
+                                                           unsigned long long* s_part) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long y = __shfl_xor(v, off);
+        v = MAX ? (v > y ? v : y) : v + y;
+    }
+    if (o.wave) return v;
+    if ((threadIdx.x & 63u) == 0) s_part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned long long r = s_part[0];
+#pragma unroll
+    for (uint32_t w = 1; w < kBankLanes / 64; ++w) r = MAX ? (r > s_part[w] ? r : s_part[w]) : r + s_part[w];
+    __syncthreads();
+    return r;
+}
+
+// Calls body(item, live, f, valid) for every listed item this owner takes: live = the item
+// exists (a wave past the end of the list idles), f = its filter (ids == NULL: item itself),
+// valid = live and f < n_filters (a bad id sets status[1] and is skipped).  The loop bound is
+// the same for every lane of a workgroup, so body may use barriers when the owner is one.
+template <typename Body>
+__device__ __forceinline__ void for_owned(const Owner& o, const uint32_t* __restrict__ ids, uint64_t count,
+                                          uint64_t n_filters, uint32_t* __restrict__ status, Body&& body) {
+    const uint32_t per = o.wave ? kBankLanes / 64 : 1u;
+    for (uint64_t base = (uint64_t)blockIdx.x * per; base < count; base += (uint64_t)gridDim.x * per) {
+        const uint64_t item = base + (o.wave ? (threadIdx.x >> 6) : 0u);
+        const bool live = item < count;
+        const uint64_t f = live ? (ids ? (uint64_t)ids[item] : item) : 0;
+        const bool valid = live && f < n_filters;
+        if (live && !valid && o.lane == 0) status[1] = 1u;
+        body(item, live, f, valid);
+    }
+}
+
+// out[item] = BITCOUNT of the item's filter (0 for a refused id).
+__global__ __launch_bounds__(kBankLanes) void bank_bitcount_kernel(const uint4* __restrict__ bits, uint64_t stride_vec,
+                                                                   uint64_t n_filters, const uint32_t* __restrict__ ids,
+                                                                   uint64_t count, unsigned long long* __restrict__ out,
+                                                                   uint32_t* __restrict__ status) {
+    __shared__ unsigned long long s_part[kBankLanes / 64];
+    const Owner o = bank_owner(stride_vec);
+    for_owned(o, ids, count, n_filters, status, [&](uint64_t item, bool live, uint64_t f, bool valid) {
+        unsigned long long acc = 0;
+        if (valid) {
+            const uint4* __restrict__ p = bits + f * stride_vec;
+#pragma unroll 4
+            for (uint64_t v = o.lane; v < stride_vec; v += o.lanes) acc += popc4(p[v]);
+        }
+        acc = owner_reduce<false>(acc, o, s_part);
+        if (live && o.lane == 0) out[item] = acc;
+    });
+}
+
+__global__ __launch_bounds__(kBankLanes) void bank_clear_kernel(uint4* __restrict__ bits, uint64_t stride_vec,
+                                                                uint64_t n_filters, const uint32_t* __restrict__ ids,
+                                                                uint64_t count, uint32_t* __restrict__ status) {
+    const Owner o = bank_owner(stride_vec);
+    for_owned(o, ids, count, n_filters, status, [&](uint64_t, bool, uint64_t f, bool valid) {
+        if (!valid) return;
+        uint4* __restrict__ p = bits + f * stride_vec;
+        for (uint64_t v = o.lane; v < stride_vec; v += o.lanes) p[v] = make_uint4(0u, 0u, 0u, 0u);
+    });
+}
+
+// Export: the item's filter copied to dst + item * stride and its trimmed Redis length (last
+// non-zero byte + 1, 0 for an empty filter) to lens[item].  A refused id exports zeros.
+__global__ __launch_bounds__(kBankLanes) void bank_gather_kernel(const uint4* __restrict__ bits, uint64_t stride_vec,
+                                                                 uint64_t n_filters, const uint32_t* __restrict__ ids,
+                                                                 uint64_t count, uint4* __restrict__ dst,
+                                                                 unsigned long long* __restrict__ lens,
+                                                                 uint32_t* __restrict__ status) {
+    __shared__ unsigned long long s_part[kBankLanes / 64];
+    const Owner o = bank_owner(stride_vec);
+    for_owned(o, ids, count, n_filters, status, [&](uint64_t item, bool live, uint64_t f, bool valid) {
+        unsigned long long last = 0;
+        if (live) {
+            const uint4* __restrict__ p = bits + f * stride_vec;   // read only when valid
+            uint4* __restrict__ d = dst + item * stride_vec;
+            for (uint64_t v = o.lane; v < stride_vec; v += o.lanes) {
+                const uint4 x = valid ? p[v] : make_uint4(0u, 0u, 0u, 0u);
+                d[v] = x;
+                const uint32_t lb = last_byte(x);
+                if (lb) last = v * 16 + lb;   // v grows: the lane's last non-zero vector wins
+            }
+        }
+        last = owner_reduce<true>(last, o, s_part);
+        if (live && o.lane == 0) lens[item] = last;
+    });
+}
+
+// Import: the first lens[item] bytes of src + item * stride replace (zero-filled to stride) or
+// are ORed into the item's filter.  One writer per filter when the listed ids are distinct.
+template <bool OR>
+__global__ __launch_bounds__(kBankLanes) void bank_scatter_kernel(uint4* __restrict__ bits, uint64_t stride_vec,
+                                                                  uint64_t n_filters, const uint32_t* __restrict__ ids,
+                                                                  uint64_t count, const uint4* __restrict__ src,
+                                                                  const unsigned long long* __restrict__ lens,
+                                                                  uint32_t* __restrict__ status) {
+    const Owner o = bank_owner(stride_vec);
+    for_owned(o, ids, count, n_filters, status, [&](uint64_t item, bool, uint64_t f, bool valid) {
+        if (!valid) return;
+        const unsigned long long cap = stride_vec * 16;
+        const unsigned long long len = lens[item] < cap ? lens[item] : cap;
+        uint4* __restrict__ p = bits + f * stride_vec;
+        const uint4* __restrict__ s = src + item * stride_vec;
+        for (uint64_t v = o.lane; v < stride_vec; v += o.lanes) {
+            const unsigned long long at = v * 16;
+            uint4 x = make_uint4(0u, 0u, 0u, 0u);
+            if (at < len) x = keep_bytes(s[v], len - at < 16 ? (uint32_t)(len - at) : 16u);
+            if (OR) {
+                if (x.x | x.y | x.z | x.w) {
+                    const uint4 c = p[v];
+                    p[v] = make_uint4(c.x | x.x, c.y | x.y, c.z | x.z, c.w | x.w);
+                }
+            } else {
+                p[v] = x;
+            }
+        }
+    });
+}
+
+uint32_t owned_grid(uint64_t stride, uint64_t count) {
+    const uint64_t per = stride <= kWaveStrideBytes ? kBankLanes / 64 : 1;
+    const uint64_t g = (count + per - 1) / per;
+    return g > kBankMaxBlocks ? kBankMaxBlocks : (g ? (uint32_t)g : 1u);
+}
+
+}  // namespace
+
+struct bf_bank {
+    std::mutex mu;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    uint64_t m = 0, reach = 0, n_filters = 0, stride = 0, bytes = 0;
+    uint32_t k = 0;
+    uint64_t batch_keys = 0, batch_bytes = 0;
+    BfGeom g{};                        // g.bits: the whole allocation, filter f at word f * stride / 4
+    uint32_t* h_status = nullptr;      // pinned [key offsets | filter id], written by the kernels
+    uint32_t* d_status = nullptr;      // ... its device address
+    // staging of the host-pointer calls
+    uint8_t *d_keys = nullptr, *d_out = nullptr;
+    uint64_t* d_off = nullptr;
+    uint32_t* d_ids = nullptr;
+    uint64_t keys_cap = 0, n_cap = 0;
+    uint8_t* d_io = nullptr;           // export / import: [count * stride bytes | count lengths]
+    uint64_t io_cap = 0;
+    uint32_t* d_list = nullptr;        // a host call's id list
+    uint64_t list_cap = 0;
+    // calls on different streams are ordered (bf_lua's LuaOrder): each waits for the event the
+    // previous call recorded
+    hipEvent_t order_ev = nullptr;
+    hipStream_t order_stream = nullptr;
+    bool order_valid = false;
+    std::string err;
+};
+
+namespace {
+
+int bank_err(bf_bank* b, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (b) b->err = buf; else g_bank_create_error = buf;
+    return code;
+}
+
+#define BANKCHK(b, expr)                                                                            \
+    do {                                                                                            \
+        hipError_t e_ = (expr);                                                                     \
+        if (e_ != hipSuccess)                                                                       \
+            return bank_err((b), (e_ == hipErrorOutOfMemory ? BF_ENOMEM : BF_EDEVICE), "%s failed: %s", \
+                            #expr, hipGetErrorString(e_));                                          \
+    } while (0)
+
+struct BankDeviceGuard {
+    int prev = -1;
+    explicit BankDeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev);
+    }
+    ~BankDeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+struct BankOrder {
+    bf_bank* b;
+    hipStream_t s;
+    BankOrder(bf_bank* b_, hipStream_t s_) : b(b_), s(s_) {
+        if (b->order_valid && b->order_stream != s) (void)hipStreamWaitEvent(s, b->order_ev, 0);
+    }
+    ~BankOrder() {
+        if (b->order_ev && hipEventRecord(b->order_ev, s) == hipSuccess) {
+            b->order_valid = true;
+            b->order_stream = s;
+        }
+    }
+};
+
+// stride of a filter of m bits; false when it does not fit 64 bits.
+bool bank_stride(uint64_t m_bits, uint64_t* stride) {
+    const uint64_t bytes = m_bits / 8 + (m_bits % 8 ? 1 : 0);
+    if (bytes > UINT64_MAX - 127) return false;
+    *stride = (bytes + 127) / 128 * 128;
+    return true;
+}
+
+int grow(bf_bank* b, void** p, uint64_t* cap, uint64_t need) {
+    if (need <= *cap) return BF_OK;
+    // an earlier call's launches may still read the old buffer
+    BANKCHK(b, hipStreamSynchronize(b->stream));
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const uint64_t want = std::max<uint64_t>(need, 1 << 16);
+    BANKCHK(b, hipMalloc(p, want));
+    *cap = want;
+    return BF_OK;
+}
+
+int ensure_keys_io(bf_bank* b, uint64_t key_bytes, uint64_t n) {
+    int rc = grow(b, (void**)&b->d_keys, &b->keys_cap, key_bytes + 16);
+    if (rc) return rc;
+    if (n + 1 > b->n_cap) {
+        BANKCHK(b, hipStreamSynchronize(b->stream));
+        for (void* p : {(void*)b->d_off, (void*)b->d_ids, (void*)b->d_out})
+            if (p) (void)hipFree(p);
+        b->d_off = nullptr;
+        b->d_ids = nullptr;
+        b->d_out = nullptr;
+        b->n_cap = 0;
+        const uint64_t cap = std::max<uint64_t>(n + 1, 1 << 12);
+        BANKCHK(b, hipMalloc((void**)&b->d_off, cap * 8));
+        BANKCHK(b, hipMalloc((void**)&b->d_ids, cap * 4));
+        BANKCHK(b, hipMalloc((void**)&b->d_out, cap));
+        b->n_cap = cap;
+    }
+    return BF_OK;
+}
+
+int launch_keys(bf_bank* b, int op, const uint8_t* d_keys, const uint64_t* d_off, const uint32_t* d_ids, uint64_t n,
+                uint8_t* d_out8, hipStream_t s) {
+    if (n >= (1ull << 31) * (uint64_t)kBankTile) return bank_err(b, BF_EINVAL, "n too large for one launch");
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_keys);
+    const uint8_t* k16 = reinterpret_cast<const uint8_t*>(a & ~(uintptr_t)15);
+    const uint64_t bias = a & 15u;
+    const dim3 grid((uint32_t)((n + kBankTile - 1) / kBankTile)), block(kBankTile);
+    if (op == BANK_INSERT)
+        hipLaunchKernelGGL(bank_keys_kernel<BANK_INSERT>, grid, block, 0, s, b->g, b->n_filters, b->stride / 4, k16,
+                           d_off, bias, d_ids, n, d_out8, b->d_status);
+    else
+        hipLaunchKernelGGL(bank_keys_kernel<BANK_INCLUDE>, grid, block, 0, s, b->g, b->n_filters, b->stride / 4, k16,
+                           d_off, bias, d_ids, n, d_out8, b->d_status);
+    BANKCHK(b, hipGetLastError());
+    return BF_OK;
+}
+
+// The host forms' refusals (nothing is launched): bf_check_offsets' rule and every id in range.
+int check_batch(bf_bank* b, const uint8_t* keys, const uint64_t* offsets, const uint32_t* ids, uint64_t n) {
+    if (!offsets || !ids || (!keys && offsets[n] != offsets[0])) return bank_err(b, BF_EINVAL, "NULL keys / offsets / filter_ids");
+    const uint64_t lo = offsets[0], hi = offsets[n];
+    for (uint64_t j = 0; j < n; ++j) {
+        if (!key_ok(lo, offsets[j], offsets[j + 1], hi, nullptr))
+            return bank_err(b, BF_EINVAL, "key %llu: offsets must be non-decreasing and every key below 2 GiB",
+                            (unsigned long long)j);
+        if ((uint64_t)ids[j] >= b->n_filters)
+            return bank_err(b, BF_EINVAL, "key %llu: filter id %u is not below n_filters = %llu", (unsigned long long)j,
+                            ids[j], (unsigned long long)b->n_filters);
+    }
+    return BF_OK;
+}
+
+// Host-pointer insert / include?: chunks of at most batch_keys keys and batch_bytes key bytes
+// (a longer key goes alone) staged on the bank's stream.
+int run_host(bf_bank* b, int op, const uint8_t* keys, const uint64_t* offsets, const uint32_t* ids, uint64_t n,
+             uint8_t* out) {
+    if (!b) return BF_EINVAL;
+    if (n == 0) return BF_OK;
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (op == BANK_INCLUDE && !out) return bank_err(b, BF_EINVAL, "out is NULL");
+    int rc = check_batch(b, keys, offsets, ids, n);
+    if (rc) return rc;
+    BankDeviceGuard dg(b->device);
+    BankOrder bo(b, b->stream);
+    std::vector<uint64_t> rebased;
+    uint64_t a = 0;
+    while (a < n) {
+        uint64_t e = std::min<uint64_t>(n, a + b->batch_keys);
+        if (offsets[e] - offsets[a] > b->batch_bytes) {   // the longest run of keys within batch_bytes, at least one
+            e = (uint64_t)(std::upper_bound(offsets + a, offsets + e + 1, offsets[a] + b->batch_bytes) - offsets) - 1;
+            if (e <= a) e = a + 1;
+        }
+        const uint64_t cn = e - a, nbytes = offsets[e] - offsets[a];
+        if ((rc = ensure_keys_io(b, nbytes, cn))) return rc;
+        rebased.resize(cn + 1);
+        for (uint64_t j = 0; j <= cn; ++j) rebased[j] = offsets[a + j] - offsets[a];
+        if (nbytes) BANKCHK(b, hipMemcpyAsync(b->d_keys, keys + offsets[a], nbytes, hipMemcpyHostToDevice, b->stream));
+        BANKCHK(b, hipMemsetAsync(b->d_keys + nbytes, 0, 16, b->stream));
+        BANKCHK(b, hipMemcpyAsync(b->d_off, rebased.data(), (cn + 1) * 8, hipMemcpyHostToDevice, b->stream));
+        BANKCHK(b, hipMemcpyAsync(b->d_ids, ids + a, cn * 4, hipMemcpyHostToDevice, b->stream));
+        if ((rc = launch_keys(b, op, b->d_keys, b->d_off, b->d_ids, cn, out ? b->d_out : nullptr, b->stream))) return rc;
+        if (out) BANKCHK(b, hipMemcpyAsync(out + a, b->d_out, cn, hipMemcpyDeviceToHost, b->stream));
+        BANKCHK(b, hipStreamSynchronize(b->stream));   // the staging buffers and `rebased` are free again
+        a = e;
+    }
+    return BF_OK;
+}
+
+int run_dev(bf_bank* b, int op, const uint8_t* d_keys, const uint64_t* d_off, const uint32_t* d_ids, uint64_t n,
+            uint8_t* d_out, void* stream) {
+    if (!b) return BF_EINVAL;
+    if (n == 0) return BF_OK;
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (!d_keys || !d_off || !d_ids || (op == BANK_INCLUDE && !d_out)) return bank_err(b, BF_EINVAL, "NULL device pointer");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    BankDeviceGuard dg(b->device);
+    BankOrder bo(b, s);
+    return launch_keys(b, op, d_keys, d_off, d_ids, n, d_out, s);
+}
+
+// ids == NULL lists every filter in order; then count must be n_filters.
+int check_list(bf_bank* b, const uint32_t* ids, uint64_t count, bool host_ids) {
+    if (!ids) {
+        if (count != b->n_filters)
+            return bank_err(b, BF_EINVAL, "ids == NULL lists every filter: count must be n_filters = %llu, got %llu",
+                            (unsigned long long)b->n_filters, (unsigned long long)count);
+        return BF_OK;
+    }
+    if (host_ids)
+        for (uint64_t i = 0; i < count; ++i)
+            if ((uint64_t)ids[i] >= b->n_filters)
+                return bank_err(b, BF_EINVAL, "ids[%llu] = %u is not below n_filters = %llu", (unsigned long long)i, ids[i],
+                                (unsigned long long)b->n_filters);
+    return BF_OK;
+}
+
+// A host id list on the device (NULL stays NULL).
+int stage_list(bf_bank* b, const uint32_t* ids, uint64_t count, const uint32_t** d_ids) {
+    *d_ids = nullptr;
+    if (!ids || !count) return BF_OK;
+    int rc = grow(b, (void**)&b->d_list, &b->list_cap, count * 4);
+    if (rc) return rc;
+    BANKCHK(b, hipMemcpyAsync(b->d_list, ids, count * 4, hipMemcpyHostToDevice, b->stream));
+    *d_ids = b->d_list;
+    return BF_OK;
+}
+
+// ids == NULL clears every filter (one fill of the allocation; count is not read).
+int launch_clear(bf_bank* b, const uint32_t* d_ids, uint64_t count, hipStream_t s) {
+    if (!d_ids) {
+        BANKCHK(b, hipMemsetAsync(b->g.bits, 0, b->bytes, s));
+        return BF_OK;
+    }
+    if (count == 0) return BF_OK;
+    hipLaunchKernelGGL(bank_clear_kernel, dim3(owned_grid(b->stride, count)), dim3(kBankLanes), 0, s,
+                       reinterpret_cast<uint4*>(b->g.bits), b->stride / 16, b->n_filters, d_ids, count, b->d_status);
+    BANKCHK(b, hipGetLastError());
+    return BF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bf_bank_stride(uint64_t m_bits, uint64_t* stride) {
+    if (!stride || m_bits == 0 || !bank_stride(m_bits, stride)) return BF_EINVAL;
+    return BF_OK;
+}
+
+int bf_bank_create(uint64_t m_bits, uint32_t k, uint64_t n_filters, const bf_config* cfg, bf_bank** out) {
+    if (!out) return bank_err(nullptr, BF_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (m_bits == 0) return bank_err(nullptr, BF_EINVAL, "m_bits == 0 (ruby.rb:51 divides by m)");
+    if (k == 0 || k > BF_MAX_K) return bank_err(nullptr, BF_EINVAL, "k must be in [1, %u], got %u", BF_MAX_K, k);
+    if (n_filters == 0) return bank_err(nullptr, BF_EINVAL, "n_filters == 0");
+    if (n_filters > (1ull << 32)) return bank_err(nullptr, BF_EINVAL, "n_filters must be at most 2^32 (filter ids are uint32)");
+    uint64_t stride = 0, bytes = 0;
+    if (!bank_stride(m_bits, &stride) || __builtin_mul_overflow(stride, n_filters, &bytes))
+        return bank_err(nullptr, BF_EINVAL, "%llu filters of %llu bits overflow a 64-bit byte size",
+                        (unsigned long long)n_filters, (unsigned long long)m_bits);
+    if (stride / 4 > (1ull << 32)) return bank_err(nullptr, BF_EINVAL, "m_bits too large for a bank (a filter's words are indexed in 32 bits)");
+    bf_config c{};
+    if (cfg && cfg->struct_size) memcpy(&c, cfg, std::min<size_t>(cfg->struct_size, sizeof c));
+    else c.device = -1;
+    if (c.struct_size < 8) c.device = -1;
+    if (c.shard_count > 1 || c.shard_index != 0)
+        return bank_err(nullptr, BF_EINVAL, "a bank is not sharded (shard_count / shard_index)");
+    if (c.device_count != 0) return bank_err(nullptr, BF_EINVAL, "a bank lives on one device (device_count)");
+    if (c.flags != 0) return bank_err(nullptr, BF_EINVAL, "a bank takes no flags (hash engines and encoder handles are single filters), got %u", c.flags);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return bank_err(nullptr, BF_EDEVICE, "no HIP device available");
+    int dev = c.device;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (dev >= ndev) return bank_err(nullptr, BF_EINVAL, "device %d out of range (%d devices)", dev, ndev);
+    bf_bank* b = new (std::nothrow) bf_bank();
+    if (!b) return bank_err(nullptr, BF_ENOMEM, "host allocation failed");
+    b->device = dev;
+    b->m = m_bits;
+    b->k = k;
+    b->n_filters = n_filters;
+    b->stride = stride;
+    b->bytes = bytes;
+    const uint64_t maxval = (uint64_t)k * 0xFFFFFFFFull;   // ruby.rb:51 reaches k (2^32 - 1) at most
+    b->reach = std::min<uint64_t>(m_bits, maxval + 1);
+    b->batch_keys = c.batch_keys ? c.batch_keys : (1ull << 22);
+    b->batch_bytes = c.batch_bytes ? c.batch_bytes : (64ull << 20);
+    BankDeviceGuard dg(dev);
+    auto fail = [&](int code, const char* what, hipError_t e) {
+        bank_err(nullptr, code, "%s failed: %s", what, hipGetErrorString(e));
+        if (b->stream) (void)hipStreamDestroy(b->stream);
+        if (b->order_ev) (void)hipEventDestroy(b->order_ev);
+        if (b->h_status) (void)hipHostFree(b->h_status);
+        if (b->g.bits) (void)hipFree(b->g.bits);
+        delete b;
+        return code;
+    };
+    hipError_t e;
+    if ((e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking)) != hipSuccess) return fail(BF_EDEVICE, "hipStreamCreate", e);
+    if ((e = hipEventCreateWithFlags(&b->order_ev, hipEventDisableTiming)) != hipSuccess) return fail(BF_EDEVICE, "hipEventCreate", e);
+    if ((e = hipHostMalloc((void**)&b->h_status, 64, hipHostMallocDefault)) != hipSuccess) return fail(BF_ENOMEM, "hipHostMalloc", e);
+    b->h_status[0] = b->h_status[1] = 0u;
+    if ((e = hipHostGetDevicePointer((void**)&b->d_status, b->h_status, 0)) != hipSuccess) return fail(BF_EDEVICE, "hipHostGetDevicePointer", e);
+    if ((e = hipMalloc((void**)&b->g.bits, bytes)) != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? BF_ENOMEM : BF_EDEVICE, "hipMalloc(bank)", e);
+    if ((e = hipMemsetAsync(b->g.bits, 0, bytes, b->stream)) != hipSuccess) return fail(BF_EDEVICE, "hipMemset", e);
+    if ((e = hipStreamSynchronize(b->stream)) != hipSuccess) return fail(BF_EDEVICE, "hipStreamSynchronize", e);
+    b->g.m = m_bits;
+    b->g.inv_m = 1.0 / (double)m_bits;
+    b->g.k = k;
+    b->g.nomod = m_bits > maxval ? 1u : 0u;
+    b->g.mod_f32 = m_bits >= (1ull << 17) ? 1u : 0u;
+    b->g.inv_m_f = (float)(1.0 / (double)m_bits);
+    b->g.mod_sub = bf_mod_sub(m_bits, maxval);
+    b->g.shards = 1;
+    b->g.inv_shards = 1.0;
+    b->g.shards_pow2 = 1;
+    b->g.block_log2 = 20;
+    b->g.limit = m_bits;
+    b->g.key_status = b->d_status;
+    *out = b;
+    return BF_OK;
+}
+
+int bf_bank_destroy(bf_bank* b) {
+    if (!b) return BF_OK;
+    {
+        std::lock_guard<std::mutex> lk(b->mu);
+        BankDeviceGuard dg(b->device);
+        (void)hipStreamSynchronize(b->stream);
+        if (b->order_valid) (void)hipEventSynchronize(b->order_ev);
+        for (void* p : {(void*)b->g.bits, (void*)b->d_keys, (void*)b->d_out, (void*)b->d_off, (void*)b->d_ids,
+                        (void*)b->d_io, (void*)b->d_list})
+            if (p) (void)hipFree(p);
+        if (b->order_ev) (void)hipEventDestroy(b->order_ev);
+        if (b->h_status) (void)hipHostFree(b->h_status);
+        (void)hipStreamDestroy(b->stream);
+    }
+    delete b;
+    return BF_OK;
+}
+
+const char* bf_bank_last_error(const bf_bank* b) { return b ? b->err.c_str() : g_bank_create_error.c_str(); }
+
+int bf_bank_info(const bf_bank* b, uint64_t* m_bits, uint32_t* k, uint64_t* n_filters, uint64_t* stride,
+                 uint64_t* device_bytes) {
+    if (!b) return BF_EINVAL;
+    if (m_bits) *m_bits = b->m;
+    if (k) *k = b->k;
+    if (n_filters) *n_filters = b->n_filters;
+    if (stride) *stride = b->stride;
+    if (device_bytes) *device_bytes = b->bytes;
+    return BF_OK;
+}
+
+int bf_bank_stream(bf_bank* b, void** stream) {
+    if (!b || !stream) return BF_EINVAL;
+    *stream = reinterpret_cast<void*>(b->stream);
+    return BF_OK;
+}
+
+int bf_bank_sync(bf_bank* b) {
+    if (!b) return BF_EINVAL;
+    std::lock_guard<std::mutex> lk(b->mu);
+    BankDeviceGuard dg(b->device);
+    BANKCHK(b, hipStreamSynchronize(b->stream));
+    if (b->order_valid) BANKCHK(b, hipEventSynchronize(b->order_ev));   // a _dev call's stream
+    const uint32_t bad_key = __atomic_exchange_n(&b->h_status[0], 0u, __ATOMIC_ACQ_REL);
+    const uint32_t bad_id = __atomic_exchange_n(&b->h_status[1], 0u, __ATOMIC_ACQ_REL);
+    if (bad_key || bad_id)
+        return bank_err(b, BF_EINVAL, "an earlier device call met %s%s%s: those keys were skipped (no bit set, answer 0), "
+                                      "those filters left alone",
+                        bad_id ? "a filter id at or past n_filters" : "", bad_id && bad_key ? " and " : "",
+                        bad_key ? "inconsistent key offsets (offsets must be non-decreasing and every key below 2 GiB)" : "");
+    return BF_OK;
+}
+
+int bf_bank_insert_many(bf_bank* b, const uint8_t* key_bytes, const uint64_t* offsets, const uint32_t* filter_ids,
+                        uint64_t n, uint8_t* key_flipped) {
+    return run_host(b, BANK_INSERT, key_bytes, offsets, filter_ids, n, key_flipped);
+}
+
+int bf_bank_include_many(bf_bank* b, const uint8_t* key_bytes, const uint64_t* offsets, const uint32_t* filter_ids,
+                         uint64_t n, uint8_t* out) {
+    return run_host(b, BANK_INCLUDE, key_bytes, offsets, filter_ids, n, out);
+}
+
+int bf_bank_insert_many_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets,
+                            const uint32_t* d_filter_ids, uint64_t n, uint8_t* d_key_flipped, void* stream) {
+    return run_dev(b, BANK_INSERT, d_key_bytes, d_offsets, d_filter_ids, n, d_key_flipped, stream);
+}
+
+int bf_bank_include_many_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets,
+                             const uint32_t* d_filter_ids, uint64_t n, uint8_t* d_out, void* stream) {
+    return run_dev(b, BANK_INCLUDE, d_key_bytes, d_offsets, d_filter_ids, n, d_out, stream);
+}
+
+int bf_bank_clear_dev(bf_bank* b, const uint32_t* d_ids, uint64_t count, void* stream) {
+    if (!b) return BF_EINVAL;
+    std::lock_guard<std::mutex> lk(b->mu);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    BankDeviceGuard dg(b->device);
+    BankOrder bo(b, s);
+    return launch_clear(b, d_ids, count, s);
+}
+
+int bf_bank_clear(bf_bank* b, const uint32_t* ids, uint64_t count) {
+    if (!b) return BF_EINVAL;
+    std::lock_guard<std::mutex> lk(b->mu);
+    int rc = ids ? check_list(b, ids, count, true) : BF_OK;
+    if (rc) return rc;
+    if (ids && count == 0) return BF_OK;
+    BankDeviceGuard dg(b->device);
+    BankOrder bo(b, b->stream);
+    const uint32_t* d_ids = nullptr;
+    if ((rc = stage_list(b, ids, count, &d_ids))) return rc;
+    if ((rc = launch_clear(b, d_ids, count, b->stream))) return rc;
+    BANKCHK(b, hipStreamSynchronize(b->stream));   // `ids` is the caller's again
+    return BF_OK;
+}
+
+int bf_bank_bitcount_dev(bf_bank* b, const uint32_t* d_ids, uint64_t count, uint64_t* d_out, void* stream) {
+    if (!b) return BF_EINVAL;
+    std::lock_guard<std::mutex> lk(b->mu);
+    int rc = check_list(b, d_ids, count, false);
+    if (rc) return rc;
+    if (count == 0) return BF_OK;
+    if (!d_out) return bank_err(b, BF_EINVAL, "d_out is NULL");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    BankDeviceGuard dg(b->device);
+    BankOrder bo(b, s);
+    hipLaunchKernelGGL(bank_bitcount_kernel, dim3(owned_grid(b->stride, count)), dim3(kBankLanes), 0, s,
+                       reinterpret_cast<const uint4*>(b->g.bits), b->stride / 16, b->n_filters, d_ids, count,
+                       reinterpret_cast<unsigned long long*>(d_out), b->d_status);
+    BANKCHK(b, hipGetLastError());
+    return BF_OK;
+}
+
+int bf_bank_bitcount(bf_bank* b, const uint32_t* ids, uint64_t count, uint64_t* out) {
+    if (!b) return BF_EINVAL;
+    std::lock_guard<std::mutex> lk(b->mu);
+    int rc = check_list(b, ids, count, true);
+    if (rc) return rc;
+    if (count == 0) return BF_OK;
+    if (!out) return bank_err(b, BF_EINVAL, "out is NULL");
+    BankDeviceGuard dg(b->device);
+    BankOrder bo(b, b->stream);
+    const uint32_t* d_ids = nullptr;
+    if ((rc = stage_list(b, ids, count, &d_ids))) return rc;
+    if ((rc = grow(b, (void**)&b->d_io, &b->io_cap, count * 8))) return rc;
+    hipLaunchKernelGGL(bank_bitcount_kernel, dim3(owned_grid(b->stride, count)), dim3(kBankLanes), 0, b->stream,
+                       reinterpret_cast<const uint4*>(b->g.bits), b->stride / 16, b->n_filters, d_ids, count,
+                       reinterpret_cast<unsigned long long*>(b->d_io), b->d_status);
+    BANKCHK(b, hipGetLastError());
+    BANKCHK(b, hipMemcpyAsync(out, b->d_io, count * 8, hipMemcpyDeviceToHost, b->stream));
+    BANKCHK(b, hipStreamSynchronize(b->stream));
+    return BF_OK;
+}
+
+int bf_bank_export_filters(bf_bank* b, const uint32_t* ids, uint64_t count, uint8_t* buf, uint64_t* lens) {
+    if (!b) return BF_EINVAL;
+    std::lock_guard<std::mutex> lk(b->mu);
+    int rc = check_list(b, ids, count, true);
+    if (rc) return rc;
+    if (count == 0) return BF_OK;
+    if (!buf || !lens) return bank_err(b, BF_EINVAL, "buf / lens is NULL");
+    uint64_t data = 0, total = 0;
+    if (__builtin_mul_overflow(count, b->stride, &data) || __builtin_add_overflow(data, count * 8, &total))
+        return bank_err(b, BF_EINVAL, "%llu filters of %llu bytes overflow a 64-bit byte size", (unsigned long long)count,
+                        (unsigned long long)b->stride);
+    BankDeviceGuard dg(b->device);
+    BankOrder bo(b, b->stream);
+    const uint32_t* d_ids = nullptr;
+    if ((rc = stage_list(b, ids, count, &d_ids))) return rc;
+    if ((rc = grow(b, (void**)&b->d_io, &b->io_cap, total))) return rc;
+    hipLaunchKernelGGL(bank_gather_kernel, dim3(owned_grid(b->stride, count)), dim3(kBankLanes), 0, b->stream,
+                       reinterpret_cast<const uint4*>(b->g.bits), b->stride / 16, b->n_filters, d_ids, count,
+                       reinterpret_cast<uint4*>(b->d_io), reinterpret_cast<unsigned long long*>(b->d_io + data),
+                       b->d_status);
+    BANKCHK(b, hipGetLastError());
+    BANKCHK(b, hipMemcpyAsync(buf, b->d_io, data, hipMemcpyDeviceToHost, b->stream));
+    BANKCHK(b, hipMemcpyAsync(lens, b->d_io + data, count * 8, hipMemcpyDeviceToHost, b->stream));
+    BANKCHK(b, hipStreamSynchronize(b->stream));
+    return BF_OK;
+}
+
+int bf_bank_import_filters(bf_bank* b, const uint32_t* ids, uint64_t count, const uint8_t* buf, const uint64_t* lens,
+                           uint32_t mode) {
+    if (!b) return BF_EINVAL;
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (mode != BF_IMPORT_REPLACE && mode != BF_IMPORT_OR) return bank_err(b, BF_EINVAL, "bad import mode %u", mode);
+    int rc = check_list(b, ids, count, true);
+    if (rc) return rc;
+    if (count == 0) return BF_OK;
+    if (!buf || !lens) return bank_err(b, BF_EINVAL, "buf / lens is NULL");
+    // bf_import_redis' refusals, for every string before anything is written
+    const uint64_t max_bytes = (b->reach + 7) / 8;
+    for (uint64_t i = 0; i < count; ++i) {
+        if (lens[i] > max_bytes)
+            return bank_err(b, BF_ERANGE, "string %llu of %llu bytes exceeds the filter's %llu reachable bytes",
+                            (unsigned long long)i, (unsigned long long)lens[i], (unsigned long long)max_bytes);
+        if (lens[i] == max_bytes && (b->reach & 7) && (buf[i * b->stride + lens[i] - 1] & (uint8_t)(0xFFu >> (b->reach & 7))))
+            return bank_err(b, BF_ERANGE, "string %llu sets bits at offsets >= %llu", (unsigned long long)i,
+                            (unsigned long long)b->reach);
+    }
+    uint64_t data = 0, total = 0;
+    if (__builtin_mul_overflow(count, b->stride, &data) || __builtin_add_overflow(data, count * 8, &total))
+        return bank_err(b, BF_EINVAL, "%llu filters of %llu bytes overflow a 64-bit byte size", (unsigned long long)count,
+                        (unsigned long long)b->stride);
+    BankDeviceGuard dg(b->device);
+    BankOrder bo(b, b->stream);
+    const uint32_t* d_ids = nullptr;
+    if ((rc = stage_list(b, ids, count, &d_ids))) return rc;
+    if ((rc = grow(b, (void**)&b->d_io, &b->io_cap, total))) return rc;
+    BANKCHK(b, hipMemcpyAsync(b->d_io, buf, data, hipMemcpyHostToDevice, b->stream));
+    BANKCHK(b, hipMemcpyAsync(b->d_io + data, lens, count * 8, hipMemcpyHostToDevice, b->stream));
+    const dim3 grid(owned_grid(b->stride, count)), block(kBankLanes);
+    uint4* bits = reinterpret_cast<uint4*>(b->g.bits);
+    const uint4* src = reinterpret_cast<const uint4*>(b->d_io);
+    const unsigned long long* d_lens = reinterpret_cast<const unsigned long long*>(b->d_io + data);
+    if (mode == BF_IMPORT_OR)
+        hipLaunchKernelGGL(bank_scatter_kernel<true>, grid, block, 0, b->stream, bits, b->stride / 16, b->n_filters, d_ids,
+                           count, src, d_lens, b->d_status);
+    else
+        hipLaunchKernelGGL(bank_scatter_kernel<false>, grid, block, 0, b->stream, bits, b->stride / 16, b->n_filters, d_ids,
+                           count, src, d_lens, b->d_status);
+    BANKCHK(b, hipGetLastError());
+    BANKCHK(b, hipStreamSynchronize(b->stream));
+    return BF_OK;
+}
+
+}  // extern "C"
