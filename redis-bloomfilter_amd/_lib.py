@@ -7,6 +7,7 @@ driver raises ``BfHipUnavailable``.
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 import sys
 import threading
@@ -300,14 +301,72 @@ def _ptr(a: Optional[np.ndarray]):
     return a.ctypes.data
 
 
-def _check(code: int, h=None) -> None:
+def _check(code: int, h=None, last_error: str = "bf_last_error") -> None:
+    """Raise for a non-OK status, with the message of the handle family's ``*_last_error``."""
     if code == BF_OK:
         return
-    lib = load()
-    msg = lib.bf_last_error(h).decode(errors="replace") if lib else ""
+    msg = getattr(load(), last_error)(h).decode(errors="replace")
     if code in (BF_EINVAL, BF_ERANGE):
         raise ArgumentError("%s: %s" % (_STATUS.get(code), msg))
     raise BfHipError(code, msg)
+
+
+def _keys(keys: np.ndarray, offsets: np.ndarray) -> Tuple[np.ndarray, np.ndarray, int]:
+    """A packed key batch as the C ABI takes it: (uint8 keys, uint64 offsets, n)."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if offsets.ndim != 1 or len(offsets) < 1:
+        raise ArgumentError("offsets must be a 1-D array of n+1 entries")
+    n = len(offsets) - 1
+    if n and int(offsets[-1]) > len(keys):
+        raise ArgumentError("offsets point past the key buffer")
+    if len(keys) == 0:
+        keys = np.zeros(1, np.uint8)
+    return keys, offsets, n
+
+
+class _Handle:
+    """What FilterBank and LuaFilter share: the lifecycle of ``self._h`` and the stream argument
+    of the ``*_dev`` methods.  A subclass names its C functions.  (Filter keeps its own copy.)"""
+
+    _DESTROY = ""        # e.g. "bf_destroy"
+    _LAST_ERROR = ""     # e.g. "bf_last_error"
+    _STREAM = None       # e.g. "bf_stream"; None: the handle type has no own-stream getter
+    _CLOSED = "filter is closed"
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            getattr(self._lib, self._DESTROY)(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise ArgumentError(self._CLOSED)
+        return self._h
+
+    def _s(self, stream):
+        """A ``stream`` argument as the C ABI takes it: None is the handle's own stream (where
+        the handle type has one), 0 HIP's null stream."""
+        if stream is None and self._STREAM:
+            if getattr(self, "_own_stream", None) is None:
+                p = _vp()
+                _check(getattr(self._lib, self._STREAM)(self.handle, ctypes.byref(p)), self._h, self._LAST_ERROR)
+                self._own_stream = p.value or 0
+            return self._own_stream or None
+        return int(stream) or None
 
 
 class Filter:
@@ -318,6 +377,8 @@ class Filter:
     ``torch.Tensor.data_ptr()``, and a hipStream_t as an int (``stream=None``:
     the filter's own stream; ``0`` is HIP's null stream, e.g. torch's default).
     """
+
+    _keys = staticmethod(_keys)   # (kept: the module-level helper under its old name)
 
     def __init__(self, m_bits: int, k: int, device: int = -1, batch_keys: int = 0,
                  batch_bytes: int = 0, shard_count: int = 1, shard_index: int = 0,
@@ -383,19 +444,6 @@ class Filter:
         return self._h
 
     # -- host-pointer batch API
-    @staticmethod
-    def _keys(keys: np.ndarray, offsets: np.ndarray) -> Tuple[np.ndarray, np.ndarray, int]:
-        keys = np.ascontiguousarray(keys, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        if offsets.ndim != 1 or len(offsets) < 1:
-            raise ArgumentError("offsets must be a 1-D array of n+1 entries")
-        n = len(offsets) - 1
-        if n and int(offsets[-1]) > len(keys):
-            raise ArgumentError("offsets point past the key buffer")
-        if len(keys) == 0:
-            keys = np.zeros(1, np.uint8)
-        return keys, offsets, n
-
     def insert_many(self, keys: np.ndarray, offsets: np.ndarray, any_new: bool = False,
                     per_key_new: bool = False):
         keys, offsets, n = self._keys(keys, offsets)
@@ -798,16 +846,10 @@ def bank_stride(m_bits: int) -> int:
     return int(out.value)
 
 
-def _bank_check(code: int, h=None) -> None:
-    if code == BF_OK:
-        return
-    msg = load().bf_bank_last_error(h).decode(errors="replace")
-    if code in (BF_EINVAL, BF_ERANGE):
-        raise ArgumentError("%s: %s" % (_STATUS.get(code), msg))
-    raise BfHipError(code, msg)
+_bank_check = functools.partial(_check, last_error="bf_bank_last_error")
 
 
-class FilterBank:
+class FilterBank(_Handle):
     """``n_filters`` device-resident filters of one (m_bits, k) behind one handle (a ``bf_bank*``;
     see include/bfhip.h).  Filter ``f`` is a Redis string in SETBIT order at byte ``f * stride``
     of one allocation; a batch names each key's filter in ``filter_ids`` (uint32).
@@ -815,6 +857,9 @@ class FilterBank:
     Arrays are numpy as for ``Filter``; the ``*_dev`` methods take raw device addresses (ints)
     and a hipStream_t as an int (``stream=None``: the bank's own stream, ``0``: the null stream)
     and do not synchronise.  ``ids=None`` lists every filter in order."""
+
+    _DESTROY, _LAST_ERROR, _STREAM = "bf_bank_destroy", "bf_bank_last_error", "bf_bank_stream"
+    _CLOSED = "bank is closed"
 
     def __init__(self, m_bits: int, k: int, n_filters: int, device: int = -1, batch_keys: int = 0,
                  batch_bytes: int = 0):
@@ -835,48 +880,15 @@ class FilterBank:
         self.m, self.k, self.n_filters, self.stride, self.device_bytes = m.value, kk.value, nf.value, st.value, db.value
         self.device = int(device)
 
-    # -- lifecycle
-    def close(self) -> None:
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.bf_bank_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    @property
-    def handle(self):
-        if not self._h:
-            raise ArgumentError("bank is closed")
-        return self._h
-
     def sync(self) -> None:
         """Wait for the bank's work; ArgumentError (once) when a ``*_dev`` call's kernel skipped
         a key or a listed filter (an id out of range, inconsistent key offsets)."""
         _bank_check(self._lib.bf_bank_sync(self.handle), self._h)
 
-    def _s(self, stream):
-        if stream is None:
-            if getattr(self, "_own_stream", None) is None:
-                p = _vp()
-                _bank_check(self._lib.bf_bank_stream(self.handle, ctypes.byref(p)), self._h)
-                self._own_stream = p.value or 0
-            return self._own_stream or None
-        return int(stream) or None
-
     # -- host-pointer batch API
     @staticmethod
     def _batch(keys, offsets, filter_ids):
-        keys, offsets, n = Filter._keys(keys, offsets)
+        keys, offsets, n = _keys(keys, offsets)
         ids = np.ascontiguousarray(filter_ids)
         if ids.ndim != 1 or len(ids) != n:
             raise ArgumentError("filter_ids must be a 1-D array of n entries")
@@ -993,17 +1005,13 @@ def lua_index(entries, count: int) -> int:
     return int(li.value)
 
 
-def _lua_check(code: int, h=None) -> None:
-    if code == BF_OK:
-        return
-    msg = load().bf_lua_last_error(h).decode(errors="replace")
-    if code in (BF_EINVAL, BF_ERANGE):
-        raise ArgumentError("%s: %s" % (_STATUS.get(code), msg))
-    raise BfHipError(code, msg)
+_lua_check = functools.partial(_check, last_error="bf_lua_last_error")
 
 
-class LuaFilter:
+class LuaFilter(_Handle):
     """The Lua driver's scalable filter on the device (a ``bf_lua*``; see include/bfhip.h)."""
+
+    _DESTROY, _LAST_ERROR = "bf_lua_destroy", "bf_lua_last_error"   # (no own-stream getter: stream=0 by default)
 
     def __init__(self, entries, precision, device: int = -1):
         self._lib = load()
@@ -1013,32 +1021,9 @@ class LuaFilter:
         self._h = h
         self.entries, self.precision = entries, precision
 
-    def close(self) -> None:
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.bf_lua_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    @property
-    def handle(self):
-        if not self._h:
-            raise ArgumentError("filter is closed")
-        return self._h
-
     def insert_many(self, keys: np.ndarray, offsets: np.ndarray):
         """-> (per-key new flags, sorted list of layers that got a new item)."""
-        keys, offsets, n = Filter._keys(keys, offsets)
+        keys, offsets, n = _keys(keys, offsets)
         pk = np.zeros(max(n, 1), np.uint8)
         mask = ctypes.c_uint64(0)
         _lua_check(self._lib.bf_lua_insert_many(self.handle, _ptr(keys), _ptr(offsets), n, _ptr(pk),
@@ -1050,7 +1035,7 @@ class LuaFilter:
     def insert_many_changes(self, keys: np.ndarray, offsets: np.ndarray):
         """-> (per-key new flags, layers that got a new item, [(layer, bit offset), ...] of every
         bit the batch flipped, each once: the SETBITs add.lua issued that changed something)."""
-        keys, offsets, n = Filter._keys(keys, offsets)
+        keys, offsets, n = _keys(keys, offsets)
         pk = np.zeros(max(n, 1), np.uint8)
         mask = ctypes.c_uint64(0)
         cap = max(64 * n, 1)   # BF_MAX_K probes per key at most
@@ -1065,7 +1050,7 @@ class LuaFilter:
         return pk[:n], [i + 1 for i in range(64) if mask.value >> i & 1], pairs
 
     def include_many(self, keys: np.ndarray, offsets: np.ndarray) -> np.ndarray:
-        keys, offsets, n = Filter._keys(keys, offsets)
+        keys, offsets, n = _keys(keys, offsets)
         out = np.zeros(max(n, 1), np.uint8)
         _lua_check(self._lib.bf_lua_include_many(self.handle, _ptr(keys), _ptr(offsets), n, _ptr(out)), self._h)
         return out[:n]
@@ -1076,12 +1061,12 @@ class LuaFilter:
         """add.lua over n device keys; returns the layers that got a new item."""
         mask = ctypes.c_uint64()
         _lua_check(self._lib.bf_lua_insert_many_dev(self.handle, d_keys, d_offsets, int(n), d_per_key_new or None,
-                                                    ctypes.byref(mask), int(stream) or None), self._h)
+                                                    ctypes.byref(mask), self._s(stream)), self._h)
         return [i + 1 for i in range(64) if mask.value >> i & 1]
 
     def include_many_dev(self, d_keys: int, d_offsets: int, n: int, d_out: int, stream=0) -> None:
         _lua_check(self._lib.bf_lua_include_many_dev(self.handle, d_keys, d_offsets, int(n), d_out,
-                                                     int(stream) or None), self._h)
+                                                     self._s(stream)), self._h)
 
     def profile(self, enable: bool) -> None:
         _lua_check(self._lib.bf_lua_profile(self.handle, 1 if enable else 0), self._h)

@@ -20,9 +20,9 @@
 //                       shuffles; one writer per output, no global atomics.
 #include "bfhip.h"
 #include "bf_device.h"
+#include "bf_host.h"
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -303,10 +303,7 @@ uint32_t owned_grid(uint64_t stride, uint64_t count) {
 
 }  // namespace
 
-struct bf_bank {
-    std::mutex mu;
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct bf_bank : BfHostCore {   // mutex, device, stream, error, stream order: bf_host.h (the profile state idle)
     uint64_t m = 0, reach = 0, n_filters = 0, stride = 0, bytes = 0;
     uint32_t k = 0;
     uint64_t batch_keys = 0, batch_bytes = 0;
@@ -322,58 +319,15 @@ struct bf_bank {
     uint64_t io_cap = 0;
     uint32_t* d_list = nullptr;        // a host call's id list
     uint64_t list_cap = 0;
-    // calls on different streams are ordered (bf_lua's LuaOrder): each waits for the event the
-    // previous call recorded
-    hipEvent_t order_ev = nullptr;
-    hipStream_t order_stream = nullptr;
-    bool order_valid = false;
-    std::string err;
 };
 
 namespace {
 
-int bank_err(bf_bank* b, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (b) b->err = buf; else g_bank_create_error = buf;
-    return code;
+// b == NULL: a create-time error, read back with bf_bank_last_error(NULL).
+template <typename... A>
+int bank_err(bf_bank* b, int code, const char* fmt, A... a) {
+    return bf_set_err(b, &g_bank_create_error, code, fmt, a...);
 }
-
-#define BANKCHK(b, expr)                                                                            \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess)                                                                       \
-            return bank_err((b), (e_ == hipErrorOutOfMemory ? BF_ENOMEM : BF_EDEVICE), "%s failed: %s", \
-                            #expr, hipGetErrorString(e_));                                          \
-    } while (0)
-
-struct BankDeviceGuard {
-    int prev = -1;
-    explicit BankDeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~BankDeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-struct BankOrder {
-    bf_bank* b;
-    hipStream_t s;
-    BankOrder(bf_bank* b_, hipStream_t s_) : b(b_), s(s_) {
-        if (b->order_valid && b->order_stream != s) (void)hipStreamWaitEvent(s, b->order_ev, 0);
-    }
-    ~BankOrder() {
-        if (b->order_ev && hipEventRecord(b->order_ev, s) == hipSuccess) {
-            b->order_valid = true;
-            b->order_stream = s;
-        }
-    }
-};
 
 // stride of a filter of m bits; false when it does not fit 64 bits.
 bool bank_stride(uint64_t m_bits, uint64_t* stride) {
@@ -386,12 +340,12 @@ bool bank_stride(uint64_t m_bits, uint64_t* stride) {
 int grow(bf_bank* b, void** p, uint64_t* cap, uint64_t need) {
     if (need <= *cap) return BF_OK;
     // an earlier call's launches may still read the old buffer
-    BANKCHK(b, hipStreamSynchronize(b->stream));
+    HIPCHK(b, hipStreamSynchronize(b->stream));
     if (*p) (void)hipFree(*p);
     *p = nullptr;
     *cap = 0;
     const uint64_t want = std::max<uint64_t>(need, 1 << 16);
-    BANKCHK(b, hipMalloc(p, want));
+    HIPCHK(b, hipMalloc(p, want));
     *cap = want;
     return BF_OK;
 }
@@ -400,7 +354,7 @@ int ensure_keys_io(bf_bank* b, uint64_t key_bytes, uint64_t n) {
     int rc = grow(b, (void**)&b->d_keys, &b->keys_cap, key_bytes + 16);
     if (rc) return rc;
     if (n + 1 > b->n_cap) {
-        BANKCHK(b, hipStreamSynchronize(b->stream));
+        HIPCHK(b, hipStreamSynchronize(b->stream));
         for (void* p : {(void*)b->d_off, (void*)b->d_ids, (void*)b->d_out})
             if (p) (void)hipFree(p);
         b->d_off = nullptr;
@@ -408,9 +362,9 @@ int ensure_keys_io(bf_bank* b, uint64_t key_bytes, uint64_t n) {
         b->d_out = nullptr;
         b->n_cap = 0;
         const uint64_t cap = std::max<uint64_t>(n + 1, 1 << 12);
-        BANKCHK(b, hipMalloc((void**)&b->d_off, cap * 8));
-        BANKCHK(b, hipMalloc((void**)&b->d_ids, cap * 4));
-        BANKCHK(b, hipMalloc((void**)&b->d_out, cap));
+        HIPCHK(b, hipMalloc((void**)&b->d_off, cap * 8));
+        HIPCHK(b, hipMalloc((void**)&b->d_ids, cap * 4));
+        HIPCHK(b, hipMalloc((void**)&b->d_out, cap));
         b->n_cap = cap;
     }
     return BF_OK;
@@ -419,9 +373,8 @@ int ensure_keys_io(bf_bank* b, uint64_t key_bytes, uint64_t n) {
 int launch_keys(bf_bank* b, int op, const uint8_t* d_keys, const uint64_t* d_off, const uint32_t* d_ids, uint64_t n,
                 uint8_t* d_out8, hipStream_t s) {
     if (n >= (1ull << 31) * (uint64_t)kBankTile) return bank_err(b, BF_EINVAL, "n too large for one launch");
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_keys);
-    const uint8_t* k16 = reinterpret_cast<const uint8_t*>(a & ~(uintptr_t)15);
-    const uint64_t bias = a & 15u;
+    uint64_t bias = 0;
+    const uint8_t* k16 = align_keys(d_keys, &bias);
     const dim3 grid((uint32_t)((n + kBankTile - 1) / kBankTile)), block(kBankTile);
     if (op == BANK_INSERT)
         hipLaunchKernelGGL(bank_keys_kernel<BANK_INSERT>, grid, block, 0, s, b->g, b->n_filters, b->stride / 4, k16,
@@ -429,7 +382,7 @@ int launch_keys(bf_bank* b, int op, const uint8_t* d_keys, const uint64_t* d_off
     else
         hipLaunchKernelGGL(bank_keys_kernel<BANK_INCLUDE>, grid, block, 0, s, b->g, b->n_filters, b->stride / 4, k16,
                            d_off, bias, d_ids, n, d_out8, b->d_status);
-    BANKCHK(b, hipGetLastError());
+    HIPCHK(b, hipGetLastError());
     return BF_OK;
 }
 
@@ -454,12 +407,11 @@ int run_host(bf_bank* b, int op, const uint8_t* keys, const uint64_t* offsets, c
              uint8_t* out) {
     if (!b) return BF_EINVAL;
     if (n == 0) return BF_OK;
-    std::lock_guard<std::mutex> lk(b->mu);
+    CallScope cs(b);
     if (op == BANK_INCLUDE && !out) return bank_err(b, BF_EINVAL, "out is NULL");
     int rc = check_batch(b, keys, offsets, ids, n);
     if (rc) return rc;
-    BankDeviceGuard dg(b->device);
-    BankOrder bo(b, b->stream);
+    if (int orc = cs.open(b->stream)) return orc;
     std::vector<uint64_t> rebased;
     uint64_t a = 0;
     while (a < n) {
@@ -472,13 +424,13 @@ int run_host(bf_bank* b, int op, const uint8_t* keys, const uint64_t* offsets, c
         if ((rc = ensure_keys_io(b, nbytes, cn))) return rc;
         rebased.resize(cn + 1);
         for (uint64_t j = 0; j <= cn; ++j) rebased[j] = offsets[a + j] - offsets[a];
-        if (nbytes) BANKCHK(b, hipMemcpyAsync(b->d_keys, keys + offsets[a], nbytes, hipMemcpyHostToDevice, b->stream));
-        BANKCHK(b, hipMemsetAsync(b->d_keys + nbytes, 0, 16, b->stream));
-        BANKCHK(b, hipMemcpyAsync(b->d_off, rebased.data(), (cn + 1) * 8, hipMemcpyHostToDevice, b->stream));
-        BANKCHK(b, hipMemcpyAsync(b->d_ids, ids + a, cn * 4, hipMemcpyHostToDevice, b->stream));
+        if (nbytes) HIPCHK(b, hipMemcpyAsync(b->d_keys, keys + offsets[a], nbytes, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(b, hipMemsetAsync(b->d_keys + nbytes, 0, 16, b->stream));
+        HIPCHK(b, hipMemcpyAsync(b->d_off, rebased.data(), (cn + 1) * 8, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(b, hipMemcpyAsync(b->d_ids, ids + a, cn * 4, hipMemcpyHostToDevice, b->stream));
         if ((rc = launch_keys(b, op, b->d_keys, b->d_off, b->d_ids, cn, out ? b->d_out : nullptr, b->stream))) return rc;
-        if (out) BANKCHK(b, hipMemcpyAsync(out + a, b->d_out, cn, hipMemcpyDeviceToHost, b->stream));
-        BANKCHK(b, hipStreamSynchronize(b->stream));   // the staging buffers and `rebased` are free again
+        if (out) HIPCHK(b, hipMemcpyAsync(out + a, b->d_out, cn, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(b, hipStreamSynchronize(b->stream));   // the staging buffers and `rebased` are free again
         a = e;
     }
     return BF_OK;
@@ -488,11 +440,10 @@ int run_dev(bf_bank* b, int op, const uint8_t* d_keys, const uint64_t* d_off, co
             uint8_t* d_out, void* stream) {
     if (!b) return BF_EINVAL;
     if (n == 0) return BF_OK;
-    std::lock_guard<std::mutex> lk(b->mu);
+    CallScope cs(b);
     if (!d_keys || !d_off || !d_ids || (op == BANK_INCLUDE && !d_out)) return bank_err(b, BF_EINVAL, "NULL device pointer");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    BankDeviceGuard dg(b->device);
-    BankOrder bo(b, s);
+    if (int orc = cs.open(s)) return orc;
     return launch_keys(b, op, d_keys, d_off, d_ids, n, d_out, s);
 }
 
@@ -518,7 +469,7 @@ int stage_list(bf_bank* b, const uint32_t* ids, uint64_t count, const uint32_t**
     if (!ids || !count) return BF_OK;
     int rc = grow(b, (void**)&b->d_list, &b->list_cap, count * 4);
     if (rc) return rc;
-    BANKCHK(b, hipMemcpyAsync(b->d_list, ids, count * 4, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(b, hipMemcpyAsync(b->d_list, ids, count * 4, hipMemcpyHostToDevice, b->stream));
     *d_ids = b->d_list;
     return BF_OK;
 }
@@ -526,13 +477,13 @@ int stage_list(bf_bank* b, const uint32_t* ids, uint64_t count, const uint32_t**
 // ids == NULL clears every filter (one fill of the allocation; count is not read).
 int launch_clear(bf_bank* b, const uint32_t* d_ids, uint64_t count, hipStream_t s) {
     if (!d_ids) {
-        BANKCHK(b, hipMemsetAsync(b->g.bits, 0, b->bytes, s));
+        HIPCHK(b, hipMemsetAsync(b->g.bits, 0, b->bytes, s));
         return BF_OK;
     }
     if (count == 0) return BF_OK;
     hipLaunchKernelGGL(bank_clear_kernel, dim3(owned_grid(b->stride, count)), dim3(kBankLanes), 0, s,
                        reinterpret_cast<uint4*>(b->g.bits), b->stride / 16, b->n_filters, d_ids, count, b->d_status);
-    BANKCHK(b, hipGetLastError());
+    HIPCHK(b, hipGetLastError());
     return BF_OK;
 }
 
@@ -582,7 +533,7 @@ int bf_bank_create(uint64_t m_bits, uint32_t k, uint64_t n_filters, const bf_con
     b->reach = std::min<uint64_t>(m_bits, maxval + 1);
     b->batch_keys = c.batch_keys ? c.batch_keys : (1ull << 22);
     b->batch_bytes = c.batch_bytes ? c.batch_bytes : (64ull << 20);
-    BankDeviceGuard dg(dev);
+    DeviceGuard dg(dev);
     auto fail = [&](int code, const char* what, hipError_t e) {
         bank_err(nullptr, code, "%s failed: %s", what, hipGetErrorString(e));
         if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -623,7 +574,7 @@ int bf_bank_destroy(bf_bank* b) {
     if (!b) return BF_OK;
     {
         std::lock_guard<std::mutex> lk(b->mu);
-        BankDeviceGuard dg(b->device);
+        DeviceGuard dg(b->device);
         (void)hipStreamSynchronize(b->stream);
         if (b->order_valid) (void)hipEventSynchronize(b->order_ev);
         for (void* p : {(void*)b->g.bits, (void*)b->d_keys, (void*)b->d_out, (void*)b->d_off, (void*)b->d_ids,
@@ -658,10 +609,10 @@ int bf_bank_stream(bf_bank* b, void** stream) {
 
 int bf_bank_sync(bf_bank* b) {
     if (!b) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(b->mu);
-    BankDeviceGuard dg(b->device);
-    BANKCHK(b, hipStreamSynchronize(b->stream));
-    if (b->order_valid) BANKCHK(b, hipEventSynchronize(b->order_ev));   // a _dev call's stream
+    CallScope cs(b);
+    if (int drc = cs.device()) return drc;
+    HIPCHK(b, hipStreamSynchronize(b->stream));
+    if (b->order_valid) HIPCHK(b, hipEventSynchronize(b->order_ev));   // a _dev call's stream
     const uint32_t bad_key = __atomic_exchange_n(&b->h_status[0], 0u, __ATOMIC_ACQ_REL);
     const uint32_t bad_id = __atomic_exchange_n(&b->h_status[1], 0u, __ATOMIC_ACQ_REL);
     if (bad_key || bad_id)
@@ -694,69 +645,65 @@ int bf_bank_include_many_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint6
 
 int bf_bank_clear_dev(bf_bank* b, const uint32_t* d_ids, uint64_t count, void* stream) {
     if (!b) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(b->mu);
+    CallScope cs(b);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    BankDeviceGuard dg(b->device);
-    BankOrder bo(b, s);
+    if (int orc = cs.open(s)) return orc;
     return launch_clear(b, d_ids, count, s);
 }
 
 int bf_bank_clear(bf_bank* b, const uint32_t* ids, uint64_t count) {
     if (!b) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(b->mu);
+    CallScope cs(b);
     int rc = ids ? check_list(b, ids, count, true) : BF_OK;
     if (rc) return rc;
     if (ids && count == 0) return BF_OK;
-    BankDeviceGuard dg(b->device);
-    BankOrder bo(b, b->stream);
+    if (int orc = cs.open(b->stream)) return orc;
     const uint32_t* d_ids = nullptr;
     if ((rc = stage_list(b, ids, count, &d_ids))) return rc;
     if ((rc = launch_clear(b, d_ids, count, b->stream))) return rc;
-    BANKCHK(b, hipStreamSynchronize(b->stream));   // `ids` is the caller's again
+    HIPCHK(b, hipStreamSynchronize(b->stream));   // `ids` is the caller's again
     return BF_OK;
 }
 
 int bf_bank_bitcount_dev(bf_bank* b, const uint32_t* d_ids, uint64_t count, uint64_t* d_out, void* stream) {
     if (!b) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(b->mu);
+    CallScope cs(b);
     int rc = check_list(b, d_ids, count, false);
     if (rc) return rc;
     if (count == 0) return BF_OK;
     if (!d_out) return bank_err(b, BF_EINVAL, "d_out is NULL");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    BankDeviceGuard dg(b->device);
-    BankOrder bo(b, s);
+    if (int orc = cs.open(s)) return orc;
     hipLaunchKernelGGL(bank_bitcount_kernel, dim3(owned_grid(b->stride, count)), dim3(kBankLanes), 0, s,
                        reinterpret_cast<const uint4*>(b->g.bits), b->stride / 16, b->n_filters, d_ids, count,
                        reinterpret_cast<unsigned long long*>(d_out), b->d_status);
-    BANKCHK(b, hipGetLastError());
+    HIPCHK(b, hipGetLastError());
     return BF_OK;
 }
 
 int bf_bank_bitcount(bf_bank* b, const uint32_t* ids, uint64_t count, uint64_t* out) {
     if (!b) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(b->mu);
+    CallScope cs(b);
     int rc = check_list(b, ids, count, true);
     if (rc) return rc;
     if (count == 0) return BF_OK;
     if (!out) return bank_err(b, BF_EINVAL, "out is NULL");
-    BankDeviceGuard dg(b->device);
-    BankOrder bo(b, b->stream);
+    if (int orc = cs.open(b->stream)) return orc;
     const uint32_t* d_ids = nullptr;
     if ((rc = stage_list(b, ids, count, &d_ids))) return rc;
     if ((rc = grow(b, (void**)&b->d_io, &b->io_cap, count * 8))) return rc;
     hipLaunchKernelGGL(bank_bitcount_kernel, dim3(owned_grid(b->stride, count)), dim3(kBankLanes), 0, b->stream,
                        reinterpret_cast<const uint4*>(b->g.bits), b->stride / 16, b->n_filters, d_ids, count,
                        reinterpret_cast<unsigned long long*>(b->d_io), b->d_status);
-    BANKCHK(b, hipGetLastError());
-    BANKCHK(b, hipMemcpyAsync(out, b->d_io, count * 8, hipMemcpyDeviceToHost, b->stream));
-    BANKCHK(b, hipStreamSynchronize(b->stream));
+    HIPCHK(b, hipGetLastError());
+    HIPCHK(b, hipMemcpyAsync(out, b->d_io, count * 8, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(b, hipStreamSynchronize(b->stream));
     return BF_OK;
 }
 
 int bf_bank_export_filters(bf_bank* b, const uint32_t* ids, uint64_t count, uint8_t* buf, uint64_t* lens) {
     if (!b) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(b->mu);
+    CallScope cs(b);
     int rc = check_list(b, ids, count, true);
     if (rc) return rc;
     if (count == 0) return BF_OK;
@@ -765,8 +712,7 @@ int bf_bank_export_filters(bf_bank* b, const uint32_t* ids, uint64_t count, uint
     if (__builtin_mul_overflow(count, b->stride, &data) || __builtin_add_overflow(data, count * 8, &total))
         return bank_err(b, BF_EINVAL, "%llu filters of %llu bytes overflow a 64-bit byte size", (unsigned long long)count,
                         (unsigned long long)b->stride);
-    BankDeviceGuard dg(b->device);
-    BankOrder bo(b, b->stream);
+    if (int orc = cs.open(b->stream)) return orc;
     const uint32_t* d_ids = nullptr;
     if ((rc = stage_list(b, ids, count, &d_ids))) return rc;
     if ((rc = grow(b, (void**)&b->d_io, &b->io_cap, total))) return rc;
@@ -774,17 +720,17 @@ int bf_bank_export_filters(bf_bank* b, const uint32_t* ids, uint64_t count, uint
                        reinterpret_cast<const uint4*>(b->g.bits), b->stride / 16, b->n_filters, d_ids, count,
                        reinterpret_cast<uint4*>(b->d_io), reinterpret_cast<unsigned long long*>(b->d_io + data),
                        b->d_status);
-    BANKCHK(b, hipGetLastError());
-    BANKCHK(b, hipMemcpyAsync(buf, b->d_io, data, hipMemcpyDeviceToHost, b->stream));
-    BANKCHK(b, hipMemcpyAsync(lens, b->d_io + data, count * 8, hipMemcpyDeviceToHost, b->stream));
-    BANKCHK(b, hipStreamSynchronize(b->stream));
+    HIPCHK(b, hipGetLastError());
+    HIPCHK(b, hipMemcpyAsync(buf, b->d_io, data, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(b, hipMemcpyAsync(lens, b->d_io + data, count * 8, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(b, hipStreamSynchronize(b->stream));
     return BF_OK;
 }
 
 int bf_bank_import_filters(bf_bank* b, const uint32_t* ids, uint64_t count, const uint8_t* buf, const uint64_t* lens,
                            uint32_t mode) {
     if (!b) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(b->mu);
+    CallScope cs(b);
     if (mode != BF_IMPORT_REPLACE && mode != BF_IMPORT_OR) return bank_err(b, BF_EINVAL, "bad import mode %u", mode);
     int rc = check_list(b, ids, count, true);
     if (rc) return rc;
@@ -804,13 +750,12 @@ int bf_bank_import_filters(bf_bank* b, const uint32_t* ids, uint64_t count, cons
     if (__builtin_mul_overflow(count, b->stride, &data) || __builtin_add_overflow(data, count * 8, &total))
         return bank_err(b, BF_EINVAL, "%llu filters of %llu bytes overflow a 64-bit byte size", (unsigned long long)count,
                         (unsigned long long)b->stride);
-    BankDeviceGuard dg(b->device);
-    BankOrder bo(b, b->stream);
+    if (int orc = cs.open(b->stream)) return orc;
     const uint32_t* d_ids = nullptr;
     if ((rc = stage_list(b, ids, count, &d_ids))) return rc;
     if ((rc = grow(b, (void**)&b->d_io, &b->io_cap, total))) return rc;
-    BANKCHK(b, hipMemcpyAsync(b->d_io, buf, data, hipMemcpyHostToDevice, b->stream));
-    BANKCHK(b, hipMemcpyAsync(b->d_io + data, lens, count * 8, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(b, hipMemcpyAsync(b->d_io, buf, data, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(b, hipMemcpyAsync(b->d_io + data, lens, count * 8, hipMemcpyHostToDevice, b->stream));
     const dim3 grid(owned_grid(b->stride, count)), block(kBankLanes);
     uint4* bits = reinterpret_cast<uint4*>(b->g.bits);
     const uint4* src = reinterpret_cast<const uint4*>(b->d_io);
@@ -821,8 +766,8 @@ int bf_bank_import_filters(bf_bank* b, const uint32_t* ids, uint64_t count, cons
     else
         hipLaunchKernelGGL(bank_scatter_kernel<false>, grid, block, 0, b->stream, bits, b->stride / 16, b->n_filters, d_ids,
                            count, src, d_lens, b->d_status);
-    BANKCHK(b, hipGetLastError());
-    BANKCHK(b, hipStreamSynchronize(b->stream));
+    HIPCHK(b, hipGetLastError());
+    HIPCHK(b, hipStreamSynchronize(b->stream));
     return BF_OK;
 }
 

@@ -1,4 +1,6 @@
-// bf_internal.h — shared between the kernels (bf_kernels.hip) and the C ABI (bf_api.cpp).
+// bf_internal.h — shared between the kernels (the .hip files) and the host side of the C ABI
+// (bf_api.cpp, bf_multi.cpp, and the host halves of bf_lua.hip and bf_bank.hip): the geometry the
+// kernels see and the launchers.  The host plumbing of bf_lua and bf_bank is in bf_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,7 +52,7 @@ struct BfGeom {
     uint64_t  flip_tag;     // ORed into every reported offset (the Lua layout: layer << 58)
     // nullable: the handle's key-status word (pinned host memory the device writes): a hashing
     // kernel stores 1 when a key's offsets are inconsistent (bfdev::key_ok) and hashes that key
-    // as the empty string; the next call on the handle returns BF_EINVAL (bf_api.cpp)
+    // as the empty string; the next call on the handle returns BF_EINVAL (take_key_status: bf_api.cpp, bf_host.h)
     uint32_t* key_status;
 };
 

@@ -17,10 +17,10 @@
 // cut are applied, and the rest continue on the next layer.
 #include "bfhip.h"
 #include "bf_device.h"
+#include "bf_host.h"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -133,10 +133,7 @@ __global__ __launch_bounds__(1024) void lua_cut_kernel(const uint8_t* __restrict
 
 }  // namespace
 
-struct bf_lua {
-    std::mutex mu;
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct bf_lua : BfHostCore {   // mutex, device, stream, error, stream order, profile: bf_host.h
     double entries = 0, precision = 0;
     uint64_t count = 0;
     std::vector<BfGeom> layers;   // layers[n - 1]: bitset of layer n (allocated on first use)
@@ -158,52 +155,19 @@ struct bf_lua {
     uint8_t* h_stage = nullptr;              // pinned [offsets | keys] of small calls (one H2D)
     unsigned long long* d_cnt = nullptr;     // lua_count_kernel's sum (device calls)
     unsigned long long* h_cnt = nullptr;     // ... read back through pinned memory
-    uint32_t* h_key_status = nullptr;        // pinned, written by the hashing kernels (bf_api.cpp take_key_status)
+    uint32_t* h_key_status = nullptr;        // pinned, written by the hashing kernels (take_key_status)
     uint32_t* d_key_status = nullptr;        // ... its device address (every layer's BfGeom::key_status)
-    // calls on different streams (the _dev entry points take the caller's) are ordered: each
-    // waits for the event the previous call recorded, as bf_handle's calls are
-    hipEvent_t order_ev = nullptr;
-    hipStream_t order_stream = nullptr;
-    bool order_valid = false;
-    // bf_lua_profile: HIP events around every kernel, accumulated per name (per layer)
-    bool profile = false;
-    std::vector<BfMarks> prof_pending, prof_free;
-    struct ProfAcc { std::string name; double ms; uint64_t launches; };
-    std::vector<ProfAcc> prof_acc;
+    // bf_lua_profile: the per-kernel names, per layer
     std::vector<std::string> prof_names;     // "<kernel>[L<layer>]", fixed at create (stable c_str())
-    std::string err;
 };
 
 namespace {
 
-int lua_err(bf_lua* h, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf; else g_lua_create_error = buf;
-    return code;
+// h == NULL: a create-time error, read back with bf_lua_last_error(NULL).
+template <typename... A>
+int lua_err(bf_lua* h, int code, const char* fmt, A... a) {
+    return bf_set_err(h, &g_lua_create_error, code, fmt, a...);
 }
-
-#define LUACHK(h, expr)                                                                            \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return lua_err((h), (e_ == hipErrorOutOfMemory ? BF_ENOMEM : BF_EDEVICE), "%s failed: %s", \
-                           #expr, hipGetErrorString(e_));                                          \
-    } while (0)
-
-struct LuaDeviceGuard {
-    int prev = -1;
-    explicit LuaDeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~LuaDeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 // add.lua:13-15 / check.lua:9-11, in IEEE double like Lua 5.1's numbers.
 uint32_t lua_index(double entries, double count) {
@@ -255,9 +219,9 @@ int ensure_layer(bf_lua* h, uint32_t n, hipStream_t s) {
             g.bits = it->second;
             h->pool.erase(it);
         } else {
-            LUACHK(h, hipMalloc((void**)&g.bits, bytes));
+            HIPCHK(h, hipMalloc((void**)&g.bits, bytes));
         }
-        LUACHK(h, hipMemsetAsync(g.bits, 0, bytes, s));
+        HIPCHK(h, hipMemsetAsync(g.bits, 0, bytes, s));
         g.m = m;
         g.inv_m = 1.0 / (double)m;
         g.k = k;
@@ -280,7 +244,7 @@ int ensure_io(bf_lua* h, uint64_t key_bytes, uint64_t n) {
         if (h->d_keys) (void)hipFree(h->d_keys);
         h->d_keys = nullptr;
         h->keys_cap = std::max<uint64_t>(key_bytes + 16, 1 << 16) * 2;
-        LUACHK(h, hipMalloc((void**)&h->d_keys, h->keys_cap));
+        HIPCHK(h, hipMalloc((void**)&h->d_keys, h->keys_cap));
     }
     if (n + 1 > h->n_cap) {
         if (h->d_off) (void)hipFree(h->d_off);
@@ -290,37 +254,12 @@ int ensure_io(bf_lua* h, uint64_t key_bytes, uint64_t n) {
         h->d_out = nullptr;
         h->h_out = nullptr;
         h->n_cap = std::max<uint64_t>(n + 1, 1 << 12) * 2;
-        LUACHK(h, hipMalloc((void**)&h->d_off, h->n_cap * 8));
-        LUACHK(h, hipMalloc((void**)&h->d_out, h->n_cap));
-        LUACHK(h, hipHostMalloc((void**)&h->h_out, h->n_cap, hipHostMallocDefault));
+        HIPCHK(h, hipMalloc((void**)&h->d_off, h->n_cap * 8));
+        HIPCHK(h, hipMalloc((void**)&h->d_out, h->n_cap));
+        HIPCHK(h, hipHostMalloc((void**)&h->h_out, h->n_cap, hipHostMallocDefault));
     }
     return BF_OK;
 }
-
-// The key-status word the hashing kernels write (bfdev::key_ok): reported once, as BF_EINVAL,
-// by the next call on the handle (bf_api.cpp take_key_status).
-int lua_take_key_status(bf_lua* h) {
-    if (!h->h_key_status || __atomic_load_n(h->h_key_status, __ATOMIC_ACQUIRE) == 0u) return BF_OK;
-    __atomic_store_n(h->h_key_status, 0u, __ATOMIC_RELEASE);
-    return lua_err(h, BF_EINVAL, "an earlier call's key offsets were inconsistent (offsets must be non-decreasing "
-                                 "and every key below 2 GiB): those keys were hashed as empty strings");
-}
-
-// Stream order across calls (bf_api.cpp's StreamOrder): wait for the previous call's event,
-// record this call's at the end.
-struct LuaOrder {
-    bf_lua* h;
-    hipStream_t s;
-    LuaOrder(bf_lua* h_, hipStream_t s_) : h(h_), s(s_) {
-        if (h->order_valid && h->order_stream != s) (void)hipStreamWaitEvent(s, h->order_ev, 0);
-    }
-    ~LuaOrder() {
-        if (h->order_ev && hipEventRecord(h->order_ev, s) == hipSuccess) {
-            h->order_valid = true;
-            h->order_stream = s;
-        }
-    }
-};
 
 enum LuaKern { kLuaCand = 0, kLuaMark = 1, kLuaCheck = 2, kLuaCount = 3, kLuaKerns = 4 };
 const char* const kLuaKernName[kLuaKerns] = {"lua_seq_candidates", "lua_seq_mark", "lua_check", "lua_count"};
@@ -329,49 +268,20 @@ const char* lua_prof_name(const bf_lua* h, LuaKern kind, uint32_t layer) {
     return h->prof_names[(size_t)kind * kLuaMaxLayers + (layer ? layer - 1 : 0)].c_str();
 }
 
-BfMarks* lua_prof_begin(bf_lua* h, hipStream_t s) {
-    if (!h->profile) return nullptr;
-    BfMarks mk{};
-    if (!h->prof_free.empty()) {
-        mk = h->prof_free.back();
-        h->prof_free.pop_back();
-    } else {
-        for (hipEvent_t& e : mk.ev)
-            if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    }
-    mk.used = 0;
-    if (hipEventRecord(mk.ev[0], s) != hipSuccess) {
-        h->prof_free.push_back(mk);
-        return nullptr;
-    }
-    h->prof_pending.push_back(mk);
-    return &h->prof_pending.back();
-}
-
-int lua_prof_harvest(bf_lua* h) {
-    for (BfMarks& mk : h->prof_pending) {
-        if (mk.used > 0) LUACHK(h, hipEventSynchronize(mk.ev[mk.used]));
-        for (int i = 0; i < mk.used; ++i) {
-            float ms = 0.f;
-            LUACHK(h, hipEventElapsedTime(&ms, mk.ev[i], mk.ev[i + 1]));
-            auto it = std::find_if(h->prof_acc.begin(), h->prof_acc.end(),
-                                   [&](const bf_lua::ProfAcc& a) { return a.name == mk.names[i]; });
-            if (it == h->prof_acc.end()) h->prof_acc.push_back({mk.names[i], (double)ms, 1});
-            else { it->ms += ms; it->launches += 1; }
-        }
-        h->prof_free.push_back(mk);
-    }
-    h->prof_pending.clear();
-    return BF_OK;
+// An op's opening, after its argument refusals (cs already holds the mutex): the device made
+// current, stream s ordered after the handle's last work, then an earlier call's bad key offsets.
+int lua_open(CallScope& cs, bf_lua* h, hipStream_t s) {
+    if (int rc = cs.open(s)) return rc;
+    return take_key_status(h, h->h_key_status);
 }
 
 int ensure_lua_scratch(bf_lua* h, uint64_t bytes) {
     if (bytes <= h->scratch_cap) return BF_OK;
-    LUACHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     if (h->scratch) (void)hipFree(h->scratch);
     h->scratch = nullptr;
     h->scratch_cap = 0;
-    LUACHK(h, hipMalloc(&h->scratch, bytes));
+    HIPCHK(h, hipMalloc(&h->scratch, bytes));
     h->scratch_cap = bytes;
     return BF_OK;
 }
@@ -391,23 +301,23 @@ int stage_keys(bf_lua* h, const uint8_t* keys, const uint64_t* offsets, uint64_t
     if (rc) return rc;
     if (n <= kLuaSmallKeys && nbytes <= kLuaSmallBytes) {
         const uint64_t off_bytes = (kLuaSmallKeys + 1) * 8;
-        if (!h->h_stage) LUACHK(h, hipHostMalloc((void**)&h->h_stage, off_bytes + kLuaSmallBytes + 16,
+        if (!h->h_stage) HIPCHK(h, hipHostMalloc((void**)&h->h_stage, off_bytes + kLuaSmallBytes + 16,
                                                  hipHostMallocDefault));
         uint64_t* ho = reinterpret_cast<uint64_t*>(h->h_stage);
         for (uint64_t j = 0; j <= n; ++j) ho[j] = offsets[j] - base;
         uint8_t* hk = h->h_stage + off_bytes;
         if (nbytes) memcpy(hk, keys + base, nbytes);
         memset(hk + nbytes, 0, 16);
-        LUACHK(h, hipMemcpyAsync(h->d_off, ho, (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
-        LUACHK(h, hipMemcpyAsync(h->d_keys, hk, nbytes + 16, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_off, ho, (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_keys, hk, nbytes + 16, hipMemcpyHostToDevice, h->stream));
         return BF_OK;
     }
     std::vector<uint64_t> rebased(n + 1);
     for (uint64_t j = 0; j <= n; ++j) rebased[j] = offsets[j] - base;
-    if (nbytes) LUACHK(h, hipMemcpyAsync(h->d_keys, keys + base, nbytes, hipMemcpyHostToDevice, h->stream));
-    LUACHK(h, hipMemsetAsync(h->d_keys + nbytes, 0, 16, h->stream));
-    LUACHK(h, hipMemcpyAsync(h->d_off, rebased.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
-    LUACHK(h, hipStreamSynchronize(h->stream));   // `rebased` is freed on return
+    if (nbytes) HIPCHK(h, hipMemcpyAsync(h->d_keys, keys + base, nbytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_keys + nbytes, 0, 16, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_off, rebased.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // `rebased` is freed on return
     return BF_OK;
 }
 
@@ -447,7 +357,7 @@ int bf_lua_create(double entries, double precision, const bf_config* cfg, bf_lua
     h->device = dev;
     h->entries = entries;
     h->precision = precision;
-    LuaDeviceGuard dg(dev);
+    DeviceGuard dg(dev);
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming) != hipSuccess ||
         hipMalloc((void**)&h->d_layers, kLuaMaxLayers * sizeof(BfGeom)) != hipSuccess ||
@@ -477,17 +387,14 @@ int bf_lua_destroy(bf_lua* h) {
     if (!h) return BF_OK;
     {
         std::lock_guard<std::mutex> lk(h->mu);
-        LuaDeviceGuard dg(h->device);
+        DeviceGuard dg(h->device);
         (void)hipStreamSynchronize(h->stream);
         for (BfGeom& g : h->layers) (void)hipFree(g.bits);
         for (auto& x : h->pool) (void)hipFree(x.second);
         for (void* p : {(void*)h->d_layers, (void*)h->scratch, (void*)h->d_keys, (void*)h->d_out, (void*)h->d_off,
                         (void*)h->d_last, (void*)h->d_flips, (void*)h->d_cnt})
             if (p) (void)hipFree(p);
-        for (std::vector<BfMarks>* v : {&h->prof_pending, &h->prof_free})
-            for (BfMarks& mk : *v)
-                for (hipEvent_t e : mk.ev)
-                    if (e) (void)hipEventDestroy(e);
+        prof_destroy(h);
         if (h->order_ev) (void)hipEventDestroy(h->order_ev);
         if (h->h_cnt) (void)hipHostFree(h->h_cnt);
         if (h->h_out) (void)hipHostFree(h->h_out);
@@ -523,10 +430,10 @@ int bf_lua_layers(const bf_lua* h, uint32_t* nlayers) {
 
 int bf_lua_clear(bf_lua* h) {
     if (!h) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(h->mu);
-    LuaDeviceGuard dg(h->device);
-    LUACHK(h, hipStreamSynchronize(h->stream));
-    if (h->order_valid) LUACHK(h, hipEventSynchronize(h->order_ev));   // a _dev call's stream
+    CallScope cs(h);
+    if (int drc = cs.device()) return drc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->order_valid) HIPCHK(h, hipEventSynchronize(h->order_ev));   // a _dev call's stream
     for (size_t i = 0; i < h->layers.size(); ++i) h->pool.push_back({h->layer_bytes[i], h->layers[i].bits});
     h->layers.clear();
     h->layer_bytes.clear();
@@ -541,17 +448,17 @@ namespace {
 
 // flips (bf_lua_insert_many_changes): every bit the batch flips, (layer << 58) | offset, into
 // a device list of `cap` entries that is copied to `flips` at the end; *flip_count = all of them.
+// changes: the call is bf_lua_insert_many_changes, which needs flip_count (and flips when cap > 0).
 int lua_insert(bf_lua* h, const uint8_t* keys, const uint64_t* offsets, uint64_t n, uint8_t* per_key_new,
-               uint64_t* new_layers, uint64_t* flips, uint64_t cap, uint64_t* flip_count) {
+               uint64_t* new_layers, bool changes, uint64_t* flips, uint64_t cap, uint64_t* flip_count) {
     if (!h) return BF_EINVAL;
+    CallScope cs(h);
+    if (changes && (!flip_count || (cap && !flips))) return lua_err(h, BF_EINVAL, "NULL out_bits / count");
     if (new_layers) *new_layers = 0;
     if (flip_count) *flip_count = 0;
     if (n == 0) return BF_OK;
     if (!offsets || (!keys && offsets[n] != offsets[0])) return lua_err(h, BF_EINVAL, "NULL keys / offsets");
-    std::lock_guard<std::mutex> lk(h->mu);
-    LuaDeviceGuard dg(h->device);
-    LuaOrder lo(h, h->stream);
-    if (int krc = lua_take_key_status(h)) return krc;   // an earlier call's bad key offsets
+    if (int krc = lua_open(cs, h, h->stream)) return krc;
     int rc = stage_keys(h, keys, offsets, n);
     if (rc) return rc;
     unsigned long long* d_flips = nullptr;
@@ -560,17 +467,17 @@ int lua_insert(bf_lua* h, const uint8_t* keys, const uint64_t* offsets, uint64_t
     bool last_read = false;   // the last chunk's flags D2H also carried the flip list
     if (flips) {   // [count | cap entries], kept on the handle
         if (h->flips_cap < cap) {
-            LUACHK(h, hipStreamSynchronize(h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
             if (h->d_flips) (void)hipFree(h->d_flips);
             h->d_flips = nullptr;
             h->flips_cap = 0;
             const uint64_t c = std::max<uint64_t>(cap, kSmallFlips);
-            LUACHK(h, hipMalloc((void**)&h->d_flips, (c + 1) * 8));
+            HIPCHK(h, hipMalloc((void**)&h->d_flips, (c + 1) * 8));
             h->flips_cap = c;
         }
-        if (!h->h_flips) LUACHK(h, hipHostMalloc((void**)&h->h_flips, (kSmallFlips + 1) * 8, hipHostMallocDefault));
+        if (!h->h_flips) HIPCHK(h, hipHostMalloc((void**)&h->h_flips, (kSmallFlips + 1) * 8, hipHostMallocDefault));
         d_flips = h->d_flips;
-        LUACHK(h, hipMemsetAsync(d_flips, 0, 8, h->stream));
+        HIPCHK(h, hipMemsetAsync(d_flips, 0, 8, h->stream));
     }
     uint64_t s = 0;
     while (s < n) {
@@ -581,8 +488,8 @@ int lua_insert(bf_lua* h, const uint8_t* keys, const uint64_t* offsets, uint64_t
         const uint64_t cn = std::min<uint64_t>(n - s, bf_seq_chunk_keys(g.k));
         if ((rc = ensure_lua_scratch(h, bf_seq_scratch_bytes(cn, g.k, g.m)))) return rc;
         // which keys would set a new bit of this layer, in order (nothing applied yet)
-        BfMarks* mk = lua_prof_begin(h, h->stream);
-        LUACHK(h, bf_launch_seq_candidates(g, 1, h->d_keys, h->d_off + s, 0, cn, h->scratch, h->stream));
+        BfMarks* mk = prof_begin(h, h->stream);
+        HIPCHK(h, bf_launch_seq_candidates(g, 1, h->d_keys, h->d_off + s, 0, cn, h->scratch, h->stream));
         bf_mark(mk, h->stream, lua_prof_name(h, kLuaCand, layer));
         BfGeom ga = g;
         if (d_flips) {
@@ -596,19 +503,19 @@ int lua_insert(bf_lua* h, const uint8_t* keys, const uint64_t* offsets, uint64_t
         if (room >= cn) {
             // no key of the chunk can fill the layer before the last one: flags and apply in ONE
             // mark pass, one sync (the per-key insert's case)
-            LUACHK(h, bf_launch_seq_mark(ga, 1, cn, cn, h->scratch, h->d_out, nullptr, h->stream));
+            HIPCHK(h, bf_launch_seq_mark(ga, 1, cn, cn, h->scratch, h->d_out, nullptr, h->stream));
             bf_mark(mk, h->stream, lua_prof_name(h, kLuaMark, layer));
-            LUACHK(h, hipMemcpyAsync(h->h_out, h->d_out, cn, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->h_out, h->d_out, cn, hipMemcpyDeviceToHost, h->stream));
             if (d_flips && small_flips)
-                LUACHK(h, hipMemcpyAsync(h->h_flips, d_flips, (cap + 1) * 8, hipMemcpyDeviceToHost, h->stream));
-            LUACHK(h, hipStreamSynchronize(h->stream));
+                HIPCHK(h, hipMemcpyAsync(h->h_flips, d_flips, (cap + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
             read_now = d_flips && small_flips;
             for (uint64_t j = 0; j < cn; ++j) fresh += h->h_out[j];
         } else {
-            LUACHK(h, bf_launch_seq_mark(g, 1, cn, 0, h->scratch, h->d_out, nullptr, h->stream));
+            HIPCHK(h, bf_launch_seq_mark(g, 1, cn, 0, h->scratch, h->d_out, nullptr, h->stream));
             bf_mark(mk, h->stream, lua_prof_name(h, kLuaMark, layer));
-            LUACHK(h, hipMemcpyAsync(h->h_out, h->d_out, cn, hipMemcpyDeviceToHost, h->stream));
-            LUACHK(h, hipStreamSynchronize(h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->h_out, h->d_out, cn, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
             // cut after the key whose INCR fills the layer (add.lua:48-50); later keys go up a layer
             for (uint64_t j = 0; j < cn; ++j) {
                 fresh += h->h_out[j];
@@ -617,8 +524,8 @@ int lua_insert(bf_lua* h, const uint8_t* keys, const uint64_t* offsets, uint64_t
                     break;
                 }
             }
-            mk = lua_prof_begin(h, h->stream);
-            LUACHK(h, bf_launch_seq_mark(ga, 1, cn, take, h->scratch, nullptr, nullptr, h->stream));
+            mk = prof_begin(h, h->stream);
+            HIPCHK(h, bf_launch_seq_mark(ga, 1, cn, take, h->scratch, nullptr, nullptr, h->stream));
             bf_mark(mk, h->stream, lua_prof_name(h, kLuaMark, layer));
         }
         if (per_key_new) memcpy(per_key_new + s, h->h_out, take);
@@ -633,20 +540,17 @@ int lua_insert(bf_lua* h, const uint8_t* keys, const uint64_t* offsets, uint64_t
             c = h->h_flips[0];
             if (c <= cap && c) memcpy(flips, h->h_flips + 1, c * 8);
         } else {
-            LUACHK(h, hipMemcpyAsync(&c, d_flips, 8, hipMemcpyDeviceToHost, h->stream));
-            LUACHK(h, hipStreamSynchronize(h->stream));
-            if (c <= cap && c) LUACHK(h, hipMemcpy(flips, d_flips + 1, c * 8, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpyAsync(&c, d_flips, 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            if (c <= cap && c) HIPCHK(h, hipMemcpy(flips, d_flips + 1, c * 8, hipMemcpyDeviceToHost));
         }
         *flip_count = c;
         if (c > cap) return lua_err(h, BF_ERANGE, "%llu bits flipped, out_bits holds %llu (the insert is applied)",
                                     c, (unsigned long long)cap);
     }
-    LUACHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return BF_OK;
 }
-
-// Layers up to n exist, cleared on the caller's stream (no host sync: VERDICT r05 item 5).
-int ensure_layer_on(bf_lua* h, uint32_t n, hipStream_t s) { return ensure_layer(h, n, s); }
 
 // bf_lua_insert_many on device-resident keys (the caller's stream): add.lua's sequential
 // semantics exactly as lua_insert, with the per-key flags left on the device and the count's
@@ -656,54 +560,50 @@ int lua_insert_dev(bf_lua* h, const uint8_t* d_keys, const uint64_t* d_offsets, 
                    uint64_t* new_layers, hipStream_t s) {
     if (new_layers) *new_layers = 0;
     if (n == 0) return BF_OK;
+    CallScope cs(h);
     if (!d_keys || !d_offsets) return lua_err(h, BF_EINVAL, "NULL device pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    LuaDeviceGuard dg(h->device);
-    LuaOrder lo(h, s);
-    if (int krc = lua_take_key_status(h)) return krc;   // an earlier call's bad key offsets
+    if (int krc = lua_open(cs, h, s)) return krc;
     uint64_t bias = 0;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_keys);
-    bias = a & 15u;
-    const uint8_t* k16 = reinterpret_cast<const uint8_t*>(a & ~(uintptr_t)15);
+    const uint8_t* k16 = align_keys(d_keys, &bias);
     int rc = ensure_io(h, 0, std::min<uint64_t>(n, bf_seq_chunk_keys(1)));   // d_out / h_out for one chunk
     if (rc) return rc;
     uint64_t done = 0;
     while (done < n) {
         const uint32_t layer = lua_index(h->entries, (double)(h->count + 1));   // add.lua:6-15
-        if ((rc = ensure_layer_on(h, layer, s))) return rc;
+        if ((rc = ensure_layer(h, layer, s))) return rc;
         const BfGeom& g = h->layers[layer - 1];
         const uint64_t room = lua_layer_capacity(h->entries, layer, h->count + 1) - h->count;   // >= 1
         const uint64_t cn = std::min<uint64_t>(n - done, bf_seq_chunk_keys(g.k));
         if ((rc = ensure_io(h, 0, cn))) return rc;
         if ((rc = ensure_lua_scratch(h, bf_seq_scratch_bytes(cn, g.k, g.m)))) return rc;
         uint8_t* flags = d_per_key_new ? d_per_key_new + done : h->d_out;
-        BfMarks* mk = lua_prof_begin(h, s);
-        LUACHK(h, bf_launch_seq_candidates(g, 1, k16, d_offsets + done, bias, cn, h->scratch, s));
+        BfMarks* mk = prof_begin(h, s);
+        HIPCHK(h, bf_launch_seq_candidates(g, 1, k16, d_offsets + done, bias, cn, h->scratch, s));
         bf_mark(mk, s, lua_prof_name(h, kLuaCand, layer));
         const uint32_t grid = (uint32_t)std::min<uint64_t>((cn / 16 + 255) / 256 + 1, 256);
-        LUACHK(h, hipMemsetAsync(h->d_cnt, 0, 16, s));
+        HIPCHK(h, hipMemsetAsync(h->d_cnt, 0, 16, s));
         if (room >= cn) {   // the whole chunk lands in this layer: flags and apply in one pass
-            LUACHK(h, bf_launch_seq_mark(g, 1, cn, cn, h->scratch, flags, nullptr, s));
+            HIPCHK(h, bf_launch_seq_mark(g, 1, cn, cn, h->scratch, flags, nullptr, s));
             bf_mark(mk, s, lua_prof_name(h, kLuaMark, layer));
             hipLaunchKernelGGL(lua_count_kernel, dim3(grid), dim3(256), 0, s, flags, cn, h->d_cnt);
-            LUACHK(h, hipGetLastError());
+            HIPCHK(h, hipGetLastError());
             bf_mark(mk, s, lua_prof_name(h, kLuaCount, layer));
-            LUACHK(h, hipMemcpyAsync(h->h_cnt, h->d_cnt, 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(h, hipMemcpyAsync(h->h_cnt, h->d_cnt, 8, hipMemcpyDeviceToHost, s));
             h->h_cnt[1] = cn;
         } else {   // the chunk may fill the layer: cut after the key whose INCR fills it (add.lua:48-50)
             // flags first; the INCRs summed and the cut found on the device (lua_cut_kernel),
             // then the keys before the cut applied with that limit — one read-back, at the end
-            LUACHK(h, bf_launch_seq_mark(g, 1, cn, 0, h->scratch, flags, nullptr, s));
+            HIPCHK(h, bf_launch_seq_mark(g, 1, cn, 0, h->scratch, flags, nullptr, s));
             bf_mark(mk, s, lua_prof_name(h, kLuaMark, layer));
             hipLaunchKernelGGL(lua_count_kernel, dim3(grid), dim3(256), 0, s, flags, cn, h->d_cnt);
             hipLaunchKernelGGL(lua_cut_kernel, dim3(1), dim3(1024), 0, s, flags, cn, room, h->d_cnt);
-            LUACHK(h, hipGetLastError());
+            HIPCHK(h, hipGetLastError());
             bf_mark(mk, s, lua_prof_name(h, kLuaCount, layer));
-            LUACHK(h, bf_launch_seq_mark(g, 1, cn, cn, h->scratch, nullptr, nullptr, s, h->d_cnt + 1));
+            HIPCHK(h, bf_launch_seq_mark(g, 1, cn, cn, h->scratch, nullptr, nullptr, s, h->d_cnt + 1));
             bf_mark(mk, s, lua_prof_name(h, kLuaMark, layer));
-            LUACHK(h, hipMemcpyAsync(h->h_cnt, h->d_cnt, 16, hipMemcpyDeviceToHost, s));
+            HIPCHK(h, hipMemcpyAsync(h->h_cnt, h->d_cnt, 16, hipMemcpyDeviceToHost, s));
         }
-        LUACHK(h, hipStreamSynchronize(s));
+        HIPCHK(h, hipStreamSynchronize(s));
         const uint64_t fresh = h->h_cnt[0], take = h->h_cnt[1];
         if (take == 0 || take > cn) return lua_err(h, BF_EDEVICE, "layer %u: cut at %llu of %llu keys", layer,
                                                    (unsigned long long)take, (unsigned long long)cn);
@@ -729,39 +629,37 @@ int bf_lua_include_many_dev(bf_lua* h, const uint8_t* d_key_bytes, const uint64_
                             uint8_t* d_out, void* stream) {
     if (!h) return BF_EINVAL;
     if (n == 0) return BF_OK;
+    CallScope cs(h);
     if (!d_key_bytes || !d_offsets || !d_out) return lua_err(h, BF_EINVAL, "NULL device pointer");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> lk(h->mu);
-    LuaDeviceGuard dg(h->device);
-    LuaOrder lo(h, s);
-    if (int krc = lua_take_key_status(h)) return krc;   // an earlier call's bad key offsets
+    if (int krc = lua_open(cs, h, s)) return krc;
     if (h->count == 0) {   // check.lua:3-7
-        LUACHK(h, hipMemsetAsync(d_out, 0, n, s));
+        HIPCHK(h, hipMemsetAsync(d_out, 0, n, s));
         return BF_OK;
     }
     const uint32_t index = lua_index(h->entries, (double)h->count);   // check.lua:9-11
-    int rc = ensure_layer_on(h, index, s);
+    int rc = ensure_layer(h, index, s);
     if (rc) return rc;
     if (h->d_layers_n < index) {   // the table is pageable host memory: the copy completes on return
-        LUACHK(h, hipMemcpyAsync(h->d_layers, h->layers.data(), index * sizeof(BfGeom), hipMemcpyHostToDevice, s));
-        LUACHK(h, hipStreamSynchronize(s));
+        HIPCHK(h, hipMemcpyAsync(h->d_layers, h->layers.data(), index * sizeof(BfGeom), hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipStreamSynchronize(s));
         h->d_layers_n = index;
     }
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_key_bytes);
-    BfMarks* mk = lua_prof_begin(h, s);
+    uint64_t bias = 0;
+    const uint8_t* k16 = align_keys(d_key_bytes, &bias);
+    BfMarks* mk = prof_begin(h, s);
     hipLaunchKernelGGL(lua_check_kernel, dim3((uint32_t)((n + kLuaTile - 1) / kLuaTile)), dim3(kLuaTile), 0, s,
-                       h->d_layers, index, reinterpret_cast<const uint8_t*>(a & ~(uintptr_t)15), d_offsets,
-                       (uint64_t)(a & 15u), n, d_out, h->d_key_status);
-    LUACHK(h, hipGetLastError());
+                       h->d_layers, index, k16, d_offsets, bias, n, d_out, h->d_key_status);
+    HIPCHK(h, hipGetLastError());
     bf_mark(mk, s, lua_prof_name(h, kLuaCheck, index));
     return BF_OK;
 }
 
 int bf_lua_profile(bf_lua* h, uint32_t enable) {
     if (!h) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(h->mu);
-    LuaDeviceGuard dg(h->device);
-    int rc = lua_prof_harvest(h);
+    CallScope cs(h);
+    if (int drc = cs.device()) return drc;
+    int rc = prof_harvest(h);
     h->profile = enable != 0;
     return rc;
 }
@@ -769,84 +667,68 @@ int bf_lua_profile(bf_lua* h, uint32_t enable) {
 int bf_lua_profile_read(bf_lua* h, char* names, double* total_ms, uint64_t* launches, uint32_t cap,
                         uint32_t* n_out, uint32_t reset) {
     if (!h || !n_out) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(h->mu);
-    LuaDeviceGuard dg(h->device);
-    int rc = lua_prof_harvest(h);
-    if (rc) return rc;
-    *n_out = (uint32_t)h->prof_acc.size();
-    for (uint32_t i = 0; i < cap && i < h->prof_acc.size(); ++i) {
-        const bf_lua::ProfAcc& acc = h->prof_acc[i];
-        if (names) snprintf(names + (size_t)i * BF_PROFILE_NAME_LEN, BF_PROFILE_NAME_LEN, "%s", acc.name.c_str());
-        if (total_ms) total_ms[i] = acc.ms;
-        if (launches) launches[i] = acc.launches;
-    }
-    if (reset) h->prof_acc.clear();
-    return BF_OK;
+    CallScope cs(h);
+    if (int drc = cs.device()) return drc;
+    return prof_read(h, names, total_ms, launches, cap, n_out, reset);
 }
 
 int bf_lua_insert_many(bf_lua* h, const uint8_t* keys, const uint64_t* offsets, uint64_t n, uint8_t* per_key_new,
                        uint64_t* new_layers) {
-    return lua_insert(h, keys, offsets, n, per_key_new, new_layers, nullptr, 0, nullptr);
+    return lua_insert(h, keys, offsets, n, per_key_new, new_layers, false, nullptr, 0, nullptr);
 }
 
 int bf_lua_insert_many_changes(bf_lua* h, const uint8_t* keys, const uint64_t* offsets, uint64_t n,
                                uint8_t* per_key_new, uint64_t* new_layers, uint64_t* out_bits, uint64_t cap,
                                uint64_t* count) {
-    if (!h) return BF_EINVAL;
-    if (!count || (cap && !out_bits)) return lua_err(h, BF_EINVAL, "NULL out_bits / count");
-    return lua_insert(h, keys, offsets, n, per_key_new, new_layers, out_bits, cap, count);
+    return lua_insert(h, keys, offsets, n, per_key_new, new_layers, true, out_bits, cap, count);
 }
 
 int bf_lua_include_many(bf_lua* h, const uint8_t* keys, const uint64_t* offsets, uint64_t n, uint8_t* out) {
     if (!h) return BF_EINVAL;
     if (n == 0) return BF_OK;
+    CallScope cs(h);
     if (!offsets || !out || (!keys && offsets[n] != offsets[0])) return lua_err(h, BF_EINVAL, "NULL argument");
-    std::lock_guard<std::mutex> lk(h->mu);
     if (h->count == 0) {   // check.lua:3-7
         memset(out, 0, n);
         return BF_OK;
     }
-    LuaDeviceGuard dg(h->device);
-    LuaOrder lo(h, h->stream);
-    if (int krc = lua_take_key_status(h)) return krc;   // an earlier call's bad key offsets
+    if (int krc = lua_open(cs, h, h->stream)) return krc;
     const uint32_t index = lua_index(h->entries, (double)h->count);   // check.lua:9-11
     int rc = ensure_layer(h, index, h->stream);
     if (rc) return rc;
     if ((rc = stage_keys(h, keys, offsets, n))) return rc;
     if (h->d_layers_n < index) {   // upload the table only when a layer was added
-        LUACHK(h, hipMemcpyAsync(h->d_layers, h->layers.data(), index * sizeof(BfGeom), hipMemcpyHostToDevice,
+        HIPCHK(h, hipMemcpyAsync(h->d_layers, h->layers.data(), index * sizeof(BfGeom), hipMemcpyHostToDevice,
                                  h->stream));
         h->d_layers_n = index;
     }
-    BfMarks* mk = lua_prof_begin(h, h->stream);
+    BfMarks* mk = prof_begin(h, h->stream);
     hipLaunchKernelGGL(lua_check_kernel, dim3((uint32_t)((n + kLuaTile - 1) / kLuaTile)), dim3(kLuaTile), 0,
                        h->stream, h->d_layers, index, h->d_keys, h->d_off, (uint64_t)0, n, h->d_out,
                        h->d_key_status);
-    LUACHK(h, hipGetLastError());
+    HIPCHK(h, hipGetLastError());
     bf_mark(mk, h->stream, lua_prof_name(h, kLuaCheck, index));
-    LUACHK(h, hipMemcpyAsync(out, h->d_out, n, hipMemcpyDeviceToHost, h->stream));
-    LUACHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpyAsync(out, h->d_out, n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return BF_OK;
 }
 
 int bf_lua_export_layer(bf_lua* h, uint32_t layer, uint8_t* buf, uint64_t cap, uint64_t* len_out) {
     if (!h || !len_out) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallScope cs(h);
     *len_out = 0;
     if (layer == 0 || layer > h->layers.size()) return BF_OK;   // a layer never written: absent key
-    LuaDeviceGuard dg(h->device);
-    LuaOrder lo(h, h->stream);
-    if (int krc = lua_take_key_status(h)) return krc;   // an earlier call's bad key offsets
+    if (int krc = lua_open(cs, h, h->stream)) return krc;
     const BfGeom& g = h->layers[layer - 1];
-    LUACHK(h, hipMemsetAsync(h->d_last, 0, 8, h->stream));
-    LUACHK(h, bf_launch_last_nonzero(g.bits, h->layer_bytes[layer - 1] / 4, h->d_last, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_last, 0, 8, h->stream));
+    HIPCHK(h, bf_launch_last_nonzero(g.bits, h->layer_bytes[layer - 1] / 4, h->d_last, h->stream));
     unsigned long long last = 0;
-    LUACHK(h, hipMemcpyAsync(&last, h->d_last, 8, hipMemcpyDeviceToHost, h->stream));
-    LUACHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpyAsync(&last, h->d_last, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     uint64_t len = 0;
     if (last) {   // trim inside the last nonzero word
         uint8_t w[4];
-        LUACHK(h, hipMemcpy(w, reinterpret_cast<const uint8_t*>(g.bits) + (last - 1) * 4, 4, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(w, reinterpret_cast<const uint8_t*>(g.bits) + (last - 1) * 4, 4, hipMemcpyDeviceToHost));
         len = (last - 1) * 4 + 4;
         while (len > (last - 1) * 4 && w[len - (last - 1) * 4 - 1] == 0) --len;
     }
@@ -854,16 +736,14 @@ int bf_lua_export_layer(bf_lua* h, uint32_t layer, uint8_t* buf, uint64_t cap, u
     if (!buf) return BF_OK;
     if (cap < len) return lua_err(h, BF_ERANGE, "buffer of %llu bytes, layer string is %llu", (unsigned long long)cap,
                                   (unsigned long long)len);
-    if (len) LUACHK(h, hipMemcpy(buf, g.bits, len, hipMemcpyDeviceToHost));
+    if (len) HIPCHK(h, hipMemcpy(buf, g.bits, len, hipMemcpyDeviceToHost));
     return BF_OK;
 }
 
 int bf_lua_import_layer(bf_lua* h, uint32_t layer, const uint8_t* buf, uint64_t len) {
     if (!h || (len && !buf)) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(h->mu);
-    LuaDeviceGuard dg(h->device);
-    LuaOrder lo(h, h->stream);
-    if (int krc = lua_take_key_status(h)) return krc;   // an earlier call's bad key offsets
+    CallScope cs(h);
+    if (int krc = lua_open(cs, h, h->stream)) return krc;
     int rc = ensure_layer(h, layer, h->stream);
     if (rc) return rc;
     const BfGeom& g = h->layers[layer - 1];
@@ -872,9 +752,9 @@ int bf_lua_import_layer(bf_lua* h, uint32_t layer, const uint8_t* buf, uint64_t 
                                    (unsigned long long)len, (unsigned long long)full);
     if (len == full && (g.m & 7) && (buf[len - 1] & (0xFF >> (g.m & 7))))
         return lua_err(h, BF_EINVAL, "layer %u string sets bits at or beyond %llu", layer, (unsigned long long)g.m);
-    LUACHK(h, hipMemsetAsync(g.bits, 0, h->layer_bytes[layer - 1], h->stream));
-    if (len) LUACHK(h, hipMemcpyAsync(g.bits, buf, len, hipMemcpyHostToDevice, h->stream));
-    LUACHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemsetAsync(g.bits, 0, h->layer_bytes[layer - 1], h->stream));
+    if (len) HIPCHK(h, hipMemcpyAsync(g.bits, buf, len, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return BF_OK;
 }
 

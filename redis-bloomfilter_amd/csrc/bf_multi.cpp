@@ -17,6 +17,7 @@
 // Everything runs within one process, so the exchange needs no collective library: a
 // device-to-device copy over xGMI is the all-to-all's send/recv.
 #include "bf_multi.h"
+#include "bf_host.h"
 
 #include <hip/hip_runtime.h>
 
@@ -91,24 +92,10 @@ int sub_rc(BfMulti* mh, uint32_t d, int rc) {
     return rc;
 }
 
-#define MCHK(mh, expr)                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return fail((mh), e_ == hipErrorOutOfMemory ? BF_ENOMEM : BF_EDEVICE, "%s failed: %s", #expr, \
-                        hipGetErrorString(e_));                                                 \
-    } while (0)
-
-struct DevGuard {
-    int prev = -1;
-    explicit DevGuard(int d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != d) (void)hipSetDevice(d);
-    }
-    ~DevGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
+// HIPCHK (bf_host.h) on a multi-device handle: the message goes through its own fail().
+int bf_hip_fail(BfMulti* mh, hipError_t e, const char* expr) {
+    return fail(mh, e == hipErrorOutOfMemory ? BF_ENOMEM : BF_EDEVICE, "%s failed: %s", expr, hipGetErrorString(e));
+}
 
 template <typename T>
 int grow(BfMulti* mh, T** p, uint64_t* cap, uint64_t need) {
@@ -117,7 +104,7 @@ int grow(BfMulti* mh, T** p, uint64_t* cap, uint64_t need) {
     *p = nullptr;
     *cap = 0;
     const uint64_t c = std::max<uint64_t>(need + need / 4, 1024);
-    MCHK(mh, hipMalloc((void**)p, c * sizeof(T)));
+    HIPCHK(mh, hipMalloc((void**)p, c * sizeof(T)));
     *cap = c;
     return BF_OK;
 }
@@ -175,16 +162,16 @@ uint64_t window_cap(const BfMulti* mh, uint64_t nd) {
 static int ensure_small(BfMulti* mh, uint32_t d) {
     DevScratch& x = mh->ds[d];
     if (x.counts && x.flag) return BF_OK;
-    DevGuard g(mh->dev[d]);
-    if (!x.counts) MCHK(mh, hipMalloc((void**)&x.counts, 256 * sizeof(uint64_t)));
-    if (!x.flag) MCHK(mh, hipMalloc((void**)&x.flag, 256));
+    DeviceGuard g(mh->dev[d]);
+    if (!x.counts) HIPCHK(mh, hipMalloc((void**)&x.counts, 256 * sizeof(uint64_t)));
+    if (!x.flag) HIPCHK(mh, hipMalloc((void**)&x.flag, 256));
     return BF_OK;
 }
 
 // Allocations of one device's round (keys, offsets, windows).
 static int prepare_round(BfMulti* mh, uint32_t d, const uint8_t* keys, const uint64_t* offsets, bool want_slot) {
     DevScratch& x = mh->ds[d];
-    DevGuard g(mh->dev[d]);
+    DeviceGuard g(mh->dev[d]);
     const uint32_t nwin = mh->D * mh->nh;
     const uint64_t base = offsets[x.a];
     const uint64_t bytes = offsets[x.a + x.n] - base;
@@ -196,14 +183,14 @@ static int prepare_round(BfMulti* mh, uint32_t d, const uint8_t* keys, const uin
         if (x.slot) (void)hipFree(x.slot);
         x.slot = nullptr;
         if ((rc = grow(mh, &x.send, &x.send_cap, nwin * x.cap))) return rc;
-        MCHK(mh, hipMalloc((void**)&x.slot, x.send_cap * sizeof(uint32_t)));
+        HIPCHK(mh, hipMalloc((void**)&x.slot, x.send_cap * sizeof(uint32_t)));
     }
     x.rel.resize(x.n + 1);
     for (uint64_t j = 0; j <= x.n; ++j) x.rel[j] = offsets[x.a + j] - base;
     x.cnt.assign(nwin, 0);
-    if (bytes) MCHK(mh, hipMemcpyAsync(x.keys, keys + base, bytes, hipMemcpyHostToDevice, x.s));
-    MCHK(mh, hipMemsetAsync(x.keys + bytes, 0, 16, x.s));
-    MCHK(mh, hipMemcpyAsync(x.offs, x.rel.data(), (x.n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, x.s));
+    if (bytes) HIPCHK(mh, hipMemcpyAsync(x.keys, keys + base, bytes, hipMemcpyHostToDevice, x.s));
+    HIPCHK(mh, hipMemsetAsync(x.keys + bytes, 0, 16, x.s));
+    HIPCHK(mh, hipMemcpyAsync(x.offs, x.rel.data(), (x.n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, x.s));
     (void)want_slot;
     return BF_OK;
 }
@@ -212,18 +199,18 @@ static int prepare_round(BfMulti* mh, uint32_t d, const uint8_t* keys, const uin
 // to the host (route_wait collects them), so every device routes at the same time.
 static int route_enqueue(BfMulti* mh, uint32_t d, bool want_slot) {
     DevScratch& x = mh->ds[d];
-    DevGuard g(mh->dev[d]);
+    DeviceGuard g(mh->dev[d]);
     const uint32_t nwin = mh->D * mh->nh;
     int rc = bf_route_windows_dev(mh->sub[d], x.keys, x.offs, x.n, x.send, want_slot ? x.slot : nullptr, x.cap,
                                   x.counts, x.s);
     if (rc) return sub_rc(mh, d, rc);
-    MCHK(mh, hipMemcpyAsync(x.cnt.data(), x.counts, nwin * sizeof(uint64_t), hipMemcpyDeviceToHost, x.s));
+    HIPCHK(mh, hipMemcpyAsync(x.cnt.data(), x.counts, nwin * sizeof(uint64_t), hipMemcpyDeviceToHost, x.s));
     return BF_OK;
 }
 
 static int route_wait(BfMulti* mh, uint32_t d) {
-    DevGuard g(mh->dev[d]);
-    MCHK(mh, hipStreamSynchronize(mh->ds[d].s));
+    DeviceGuard g(mh->dev[d]);
+    HIPCHK(mh, hipStreamSynchronize(mh->ds[d].s));
     return BF_OK;
 }
 
@@ -263,20 +250,20 @@ static int partitioned_round(BfMulti* mh, const uint8_t* keys, const uint64_t* o
         for (uint32_t d = 0; d < D; ++d) {
             DevScratch& x = mh->ds[d];
             if (!x.n) continue;
-            DevGuard g(mh->dev[d]);
+            DeviceGuard g(mh->dev[d]);
             if ((rc = grow(mh, &x.back, &x.back_cap, (uint64_t)nwin * x.cap))) return rc;
         }
     // owners pull their windows (sub-range major, then source), apply or test them, and
     // (include?) push the answers back into each requester's window layout
     for (uint32_t o = 0; o < D; ++o) {
         DevScratch& y = mh->ds[o];
-        DevGuard g(mh->dev[o]);
+        DeviceGuard g(mh->dev[o]);
         uint64_t total = 0;
         for (uint32_t d = 0; d < D; ++d)
             for (uint32_t h = 0; h < nh; ++h) total += mh->ds[d].cnt[o * nh + h];
         if ((rc = grow(mh, &y.recv, &y.recv_cap, std::max<uint64_t>(total, 1)))) return rc;
         if (include && (rc = grow(mh, &y.bits, &y.bits_cap, std::max<uint64_t>(total, 1)))) return rc;
-        if (!include && any_new) MCHK(mh, hipMemsetAsync(y.flag, 0, sizeof(uint32_t), y.s));
+        if (!include && any_new) HIPCHK(mh, hipMemsetAsync(y.flag, 0, sizeof(uint32_t), y.s));
         uint64_t at = 0;
         for (uint32_t h = 0; h < nh; ++h) {
             const uint64_t h0 = at;
@@ -284,7 +271,7 @@ static int partitioned_round(BfMulti* mh, const uint8_t* keys, const uint64_t* o
                 const DevScratch& x = mh->ds[d];
                 const uint64_t c = x.cnt[o * nh + h];
                 if (!c) continue;
-                MCHK(mh, hipMemcpyPeerAsync(y.recv + at, mh->dev[o], x.send + (uint64_t)(o * nh + h) * x.cap,
+                HIPCHK(mh, hipMemcpyPeerAsync(y.recv + at, mh->dev[o], x.send + (uint64_t)(o * nh + h) * x.cap,
                                             mh->dev[d], c * sizeof(uint32_t), y.s));
                 at += c;
             }
@@ -300,21 +287,21 @@ static int partitioned_round(BfMulti* mh, const uint8_t* keys, const uint64_t* o
                     DevScratch& x = mh->ds[d];
                     const uint64_t c = x.cnt[o * nh + h];
                     if (!c) continue;
-                    MCHK(mh, hipMemcpyPeerAsync(x.back + (uint64_t)(o * nh + h) * x.cap, mh->dev[d], y.bits + bt,
+                    HIPCHK(mh, hipMemcpyPeerAsync(x.back + (uint64_t)(o * nh + h) * x.cap, mh->dev[d], y.bits + bt,
                                                 mh->dev[o], c, y.s));
                     bt += c;
                 }
             }
         }
-        MCHK(mh, hipEventRecord(y.ev, y.s));
+        HIPCHK(mh, hipEventRecord(y.ev, y.s));
     }
     if (!include) {
         for (uint32_t o = 0; o < D; ++o) {
-            DevGuard g(mh->dev[o]);
-            MCHK(mh, hipStreamSynchronize(mh->ds[o].s));
+            DeviceGuard g(mh->dev[o]);
+            HIPCHK(mh, hipStreamSynchronize(mh->ds[o].s));
             if (any_new) {
                 uint32_t f = 0;
-                MCHK(mh, hipMemcpy(&f, mh->ds[o].flag, sizeof f, hipMemcpyDeviceToHost));
+                HIPCHK(mh, hipMemcpy(&f, mh->ds[o].flag, sizeof f, hipMemcpyDeviceToHost));
                 if (f) *any_new = true;
             }
         }
@@ -324,16 +311,16 @@ static int partitioned_round(BfMulti* mh, const uint8_t* keys, const uint64_t* o
     for (uint32_t d = 0; d < D; ++d) {
         DevScratch& x = mh->ds[d];
         if (!x.n) continue;
-        DevGuard g(mh->dev[d]);
-        for (uint32_t o = 0; o < D; ++o) MCHK(mh, hipStreamWaitEvent(x.s, mh->ds[o].ev, 0));
+        DeviceGuard g(mh->dev[d]);
+        for (uint32_t o = 0; o < D; ++o) HIPCHK(mh, hipStreamWaitEvent(x.s, mh->ds[o].ev, 0));
         if ((rc = grow(mh, &x.out, &x.out_cap, x.n))) return rc;
         rc = bf_combine_windows_dev(mh->sub[d], x.back, x.slot, x.cap, nwin, x.counts, x.n, x.out, x.s);
         if (rc) return sub_rc(mh, d, rc);
-        MCHK(mh, hipMemcpyAsync(out + x.a, x.out, x.n, hipMemcpyDeviceToHost, x.s));
+        HIPCHK(mh, hipMemcpyAsync(out + x.a, x.out, x.n, hipMemcpyDeviceToHost, x.s));
     }
     for (uint32_t d = 0; d < D; ++d) {
-        DevGuard g(mh->dev[d]);
-        MCHK(mh, hipStreamSynchronize(mh->ds[d].s));
+        DeviceGuard g(mh->dev[d]);
+        HIPCHK(mh, hipStreamSynchronize(mh->ds[d].s));
     }
     return BF_OK;
 }
@@ -410,7 +397,7 @@ int bfm_create(uint64_t m_bits, uint32_t k, const bf_config& cfg, BfMulti** out,
             if (mh->dev[a] == mh->dev[b]) continue;
             int can = 0;
             if (hipDeviceCanAccessPeer(&can, mh->dev[a], mh->dev[b]) == hipSuccess && can) {
-                DevGuard g(mh->dev[a]);
+                DeviceGuard g(mh->dev[a]);
                 const hipError_t e = hipDeviceEnablePeerAccess(mh->dev[b], 0);
                 if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
             }
@@ -433,7 +420,7 @@ int bfm_create(uint64_t m_bits, uint32_t k, const bf_config& cfg, BfMulti** out,
         const int rc = bf_create(m_bits, k, &c, &h);
         if (rc) return bail(rc, std::string("device slot ") + std::to_string(d) + ": " + bf_last_error(nullptr));
         mh->sub.push_back(h);
-        DevGuard g(mh->dev[d]);
+        DeviceGuard g(mh->dev[d]);
         if (hipStreamCreateWithFlags(&mh->ds[d].s, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&mh->ds[d].ev, hipEventDisableTiming) != hipSuccess)
             return bail(BF_EDEVICE, "stream / event creation failed");
@@ -456,7 +443,7 @@ void bfm_destroy(BfMulti* mh) {
     for (uint32_t d = 0; d < mh->ds.size(); ++d) {
         DevScratch& x = mh->ds[d];
         if (!x.s) continue;   // nothing was created on this slot
-        DevGuard g(mh->dev[d]);
+        DeviceGuard g(mh->dev[d]);
         if (x.s) (void)hipStreamSynchronize(x.s);
         for (void* p : {(void*)x.keys, (void*)x.offs, (void*)x.send, (void*)x.slot, (void*)x.counts, (void*)x.recv,
                         (void*)x.bits, (void*)x.back, (void*)x.out, (void*)x.flag})

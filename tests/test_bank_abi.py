@@ -50,6 +50,23 @@ def test_create_argument_refusals_need_no_device(pkg, m, k, n, what):
     assert what in msg, msg
 
 
+def test_create_errors_are_per_family(pkg):
+    """bf_last_error(NULL), bf_bank_last_error(NULL) and bf_lua_last_error(NULL) are three
+    strings: a refused bank or Lua create leaves the single filter's create error alone."""
+    lib = pkg._lib.load()
+    E = pkg._lib.BF_EINVAL
+    h = ctypes.c_void_p()
+    assert lib.bf_create(0, 6, None, ctypes.byref(h)) == E
+    single = lib.bf_last_error(None)
+    assert b"m_bits == 0" in single
+    assert lib.bf_bank_create(9585, 6, 0, None, ctypes.byref(h)) == E
+    assert lib.bf_lua_create(-1.0, 0.01, None, ctypes.byref(h)) == E
+    assert b"n_filters == 0" in lib.bf_bank_last_error(None)
+    assert b"entries must be > 0" in lib.bf_lua_last_error(None)
+    assert lib.bf_last_error(None) == single
+    assert b"n_filters" not in single and b"entries" not in single
+
+
 @pytest.mark.parametrize("field,value", [
     ("shard_count", 2), ("shard_index", 1), ("device_count", 1),
     ("flags", 2), ("flags", 4), ("flags", 8), ("flags", 1)])   # ENGINE_MD5, ENGINE_SHA1, ENCODER, ROUTE32

@@ -106,6 +106,48 @@ def test_lua_device_entry_points_match_scripts(pkg, entries, precision, nkeys, s
         assert "lua_check" in prof and "lua_seq_candidates[L1]" in prof and "lua_seq_mark[L2]" in prof
 
 
+def test_lua_device_calls_on_side_streams(pkg):
+    """bf_lua_insert_many_dev issued alternately on two torch streams with no synchronisation
+    between them, then bf_lua_include_many_dev on a third: the handle orders its own work across
+    streams, so flags, count, layer strings and answers equal the scripts'."""
+    torch = pytest.importorskip("torch")
+    entries, precision, nkeys = 1000, 0.01, 3000
+    rng = np.random.default_rng(17)
+    keys = [int(v) for v in rng.integers(0, 10**9, nkeys)]
+    r, want_flags = script_run(pkg, keys, entries, precision)
+    cuts = np.linspace(0, nkeys, 4).astype(int)
+    dev = []
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        buf, offs = pkg.keys.pack(keys[a:b])
+        dev.append((torch.from_numpy(np.concatenate([buf, np.zeros(16, np.uint8)])).cuda(),
+                    torch.from_numpy(offs.view(np.int64)).cuda(),
+                    torch.zeros(b - a, dtype=torch.uint8, device="cuda")))
+    probe = keys[: nkeys // 2] + ["fresh-%d" % i for i in range(nkeys // 2)]
+    pb, po = pkg.keys.pack(probe)
+    pkb = torch.from_numpy(np.concatenate([pb, np.zeros(16, np.uint8)])).cuda()
+    pko = torch.from_numpy(po.view(np.int64)).cuda()
+    out = torch.empty(len(probe), dtype=torch.uint8, device="cuda")
+    s1, s2, s3 = torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with pkg.LuaFilter(entries, precision) as f:
+        for i, (kb, ko, flags) in enumerate(dev):      # alternate streams, never synchronise between
+            st = (s1 if i % 2 == 0 else s2).cuda_stream
+            f.insert_many_dev(kb.data_ptr(), ko.data_ptr(), flags.numel(), flags.data_ptr(), stream=st)
+        f.include_many_dev(pkb.data_ptr(), pko.data_ptr(), len(probe), out.data_ptr(), stream=s3.cuda_stream)
+        torch.cuda.synchronize()
+        got_flags = np.concatenate([flags.cpu().numpy().astype(bool) for _, _, flags in dev])
+        np.testing.assert_array_equal(got_flags, want_flags)
+        assert f.count == int(r.get("lbf:count"))
+        want_layers = layers_of(r, "lbf")
+        assert f.layers == len(want_layers) and len(want_layers) >= 2
+        for n, s in want_layers.items():
+            assert f.export_layer(n) == s, n
+        got = out.cpu().numpy().astype(bool)
+        want = np.array([L.check(r, "lbf", entries, precision, k) for k in probe])
+        np.testing.assert_array_equal(got, want)
+        np.testing.assert_array_equal(got, f.include_many(pb, po).astype(bool))   # = the host path
+
+
 def test_hip_lua_driver_write_through_and_interop(pkg):
     """The driver's Redis keys equal the scripts' after the same inserts (lua.rb layout), a
     driver attached to the scripts' Redis answers like check.lua, and clear drops name:*."""

@@ -40,3 +40,25 @@ def test_inserts_on_two_streams(pkg, oracle, monkeypatch, binned):
         oracle.insert_many(bits, m, k, b, o)
     assert got == oracle.redis_string(bits)
     assert ans.all()
+
+
+@pytest.mark.parametrize("make,message", [
+    (lambda pkg: pkg.Filter(9585, 6), "filter is closed"),
+    (lambda pkg: pkg.FilterBank(9585, 6, 4), "bank is closed"),
+    (lambda pkg: pkg.LuaFilter(1000, 0.01), "filter is closed"),
+], ids=["Filter", "FilterBank", "LuaFilter"])
+def test_closed_handles(pkg, make, message):
+    """The lifecycle of the three handle classes: ``.handle`` raises after ``close()``, a
+    second ``close()`` is a no-op, and the ``with`` form closes."""
+    f = make(pkg)
+    assert f.handle
+    f.close()
+    with pytest.raises(pkg.ArgumentError) as e:
+        f.handle
+    assert str(e.value) == message
+    f.close()
+    with make(pkg) as g:
+        assert g.handle
+    with pytest.raises(pkg.ArgumentError) as e:
+        g.handle
+    assert str(e.value) == message
