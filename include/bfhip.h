@@ -35,6 +35,7 @@
  *   bf_estimate_count  distinct keys behind a bit count, under the probe law of        ruby.rb:51
  *   bf_bank_*          many filters of one (m, k), one per key_name, behind one handle:
  *                      Ruby#insert / #include? / #clear per (key_name, key)     ruby.rb:15-35, 57-63
+ *                      and #include? of one key in every listed key_name (bf_bank_include_across)
  *   bf_optimal_m/_k    Redis::Bloomfilter.optimal_m / optimal_k       lib/redis/bloomfilter.rb:50-58
  *   bf_version         Redis::Bloomfilter.version                     lib/redis/bloomfilter/version.rb:6-8
  *
@@ -646,6 +647,24 @@ int  bf_lua_index(double entries, uint64_t count, uint32_t* layer);
  *                        Per key it is NOT the sequential flag (which key of several wins a bit is
  *                        unspecified; bf_insert_many's per_key_new has no counterpart here).
  *   bf_bank_include_many Ruby#include? of key j in filter filter_ids[j]: out[j] = 0 / 1   ruby.rb:20-30
+ *   bf_bank_include_across  Ruby#include? of key j in EVERY listed filter: which of the bank's   ruby.rb:20-30
+ *                        filters have seen this key.  A key's k offsets (ruby.rb:41-55) depend on
+ *                        (m, k) alone, which a bank's filters share, so the key is hashed once and
+ *                        the same k bit positions are tested in each listed filter.  Row j of
+ *                        mask (bf_bank_across_row_bytes(count) = 8 * ceil(count / 64) bytes)
+ *                        belongs to key j; list entry i is the bit of value 1 << (i & 7) of the
+ *                        row's byte i >> 3 (LSB first), 1 exactly when include? of key j in filter
+ *                        ids[i] is true.  Listed ids may come in any order and may repeat; ids ==
+ *                        NULL: entry i is filter i, count must be n_filters.  Bits count .. 8 *
+ *                        row_bytes - 1 of every row are 0 and every word of every row is written,
+ *                        so the caller does not clear the mask.  n == 0 or count == 0: BF_OK,
+ *                        nothing written.  The host form refuses (BF_EINVAL, mask untouched) a
+ *                        NULL mask or offsets, offsets that fail bf_check_offsets' rule, a listed
+ *                        id >= n_filters and n * row_bytes past 64 bits.  The _dev form refuses
+ *                        NULL or misaligned pointers (d_offsets, d_mask: 8 bytes; d_ids: 4); its
+ *                        kernel answers an all-zero row for a key whose offsets fail the rule and
+ *                        0 for a list entry >= n_filters, and sets the status word (below).
+ *   bf_bank_across_row_bytes  the bytes of one mask row of count entries (host only)
  *   bf_bank_clear        Ruby#clear (DEL key_name) of the listed filters   ruby.rb:33-35
  *                        ids == NULL: every filter (count is not read).
  *   bf_bank_bitcount     BITCOUNT key_name of the count listed filters in one launch, out[i]
@@ -688,6 +707,13 @@ int  bf_bank_include_many(bf_bank* b, const uint8_t* key_bytes, const uint64_t* 
                           uint64_t n, uint8_t* out /* n bytes, 0/1 */);
 int  bf_bank_include_many_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets,
                               const uint32_t* d_filter_ids, uint64_t n, uint8_t* d_out, void* stream);
+int  bf_bank_across_row_bytes(uint64_t count, uint64_t* bytes);
+int  bf_bank_include_across(bf_bank* b, const uint8_t* key_bytes, const uint64_t* offsets, uint64_t n,
+                            const uint32_t* ids /* nullable: all */, uint64_t count,
+                            uint8_t* mask /* n * row_bytes */);
+int  bf_bank_include_across_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets, uint64_t n,
+                                const uint32_t* d_ids /* nullable: all */, uint64_t count,
+                                uint8_t* d_mask /* n * row_bytes, 8-byte aligned */, void* stream);
 int  bf_bank_clear(bf_bank* b, const uint32_t* ids /* nullable: all */, uint64_t count);
 int  bf_bank_clear_dev(bf_bank* b, const uint32_t* d_ids /* nullable: all */, uint64_t count, void* stream);
 int  bf_bank_bitcount(bf_bank* b, const uint32_t* ids /* nullable: all */, uint64_t count, uint64_t* out);

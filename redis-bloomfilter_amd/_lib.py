@@ -169,6 +169,9 @@ SIGNATURES = {
     "bf_bank_insert_many_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
     "bf_bank_include_many": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "bf_bank_include_many_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "bf_bank_across_row_bytes": (ctypes.c_int, [_u64, _u64p]),
+    "bf_bank_include_across": (ctypes.c_int, [_vp, _vp, _vp, _u64, _vp, _u64, _vp]),
+    "bf_bank_include_across_dev": (ctypes.c_int, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp]),
     "bf_bank_clear": (ctypes.c_int, [_vp, _vp, _u64]),
     "bf_bank_clear_dev": (ctypes.c_int, [_vp, _vp, _u64, _vp]),
     "bf_bank_bitcount": (ctypes.c_int, [_vp, _vp, _u64, _vp]),
@@ -915,6 +918,29 @@ class FilterBank(_Handle):
                     self._h)
         return out[:n]
 
+    @staticmethod
+    def across_row_bytes(count: int) -> int:
+        """Bytes of one mask row of a cross query over ``count`` list entries: 8 * ceil(count / 64)
+        (bf_bank_across_row_bytes)."""
+        out = ctypes.c_uint64()
+        if not 0 <= int(count) < 1 << 64 or load().bf_bank_across_row_bytes(int(count), ctypes.byref(out)):
+            raise ArgumentError("bf_bank_across_row_bytes(%r): count must be an unsigned 64-bit integer" % (count,))
+        return int(out.value)
+
+    def include_across(self, keys: np.ndarray, offsets: np.ndarray, ids=None) -> np.ndarray:
+        """Which of the listed filters hold each key (bf_bank_include_across): a bool array of
+        shape (n, count), [j, i] = include? of key j in filter ids[i].  The key is hashed once;
+        ids may repeat and come in any order."""
+        keys, offsets, n = _keys(keys, offsets)
+        a, count = self._ids(ids)
+        row = self.across_row_bytes(count)
+        mask = np.zeros((max(n, 1), max(row, 1)), np.uint8)
+        _bank_check(self._lib.bf_bank_include_across(self.handle, _ptr(keys), _ptr(offsets), n, _ptr(a), count,
+                                                     _ptr(mask)), self._h)
+        if n == 0 or count == 0:
+            return np.zeros((n, count), bool)
+        return np.unpackbits(mask[:n, :row], axis=1, count=count, bitorder="little").astype(bool)
+
     def _ids(self, ids):
         """(uint32 array or None, count) of an id list; None lists every filter."""
         if ids is None:
@@ -976,6 +1002,14 @@ class FilterBank(_Handle):
                          stream=None) -> None:
         _bank_check(self._lib.bf_bank_include_many_dev(self.handle, d_keys, d_offsets, d_filter_ids, int(n), d_out,
                                                        self._s(stream)), self._h)
+
+    def include_across_dev(self, d_keys: int, d_offsets: int, n: int, d_mask: int, d_ids: int = 0,
+                           count: Optional[int] = None, stream=None) -> None:
+        """The cross query on ``stream``: n rows of ``across_row_bytes(count)`` bytes are written at
+        d_mask (8-byte aligned; d_ids = 0: every filter, count = n_filters)."""
+        count = self.n_filters if count is None else int(count)
+        _bank_check(self._lib.bf_bank_include_across_dev(self.handle, d_keys, d_offsets, int(n), d_ids or None, count,
+                                                         d_mask or None, self._s(stream)), self._h)
 
     def clear_dev(self, d_ids: int = 0, count: int = 0, stream=None) -> None:
         _bank_check(self._lib.bf_bank_clear_dev(self.handle, d_ids or None, int(count), self._s(stream)), self._h)

@@ -5,7 +5,8 @@ In the reference ``key_name`` names a filter (lib/redis/bloomfilter.rb:14, ruby.
 and an application keeps one per tenant, per day or per feed.  A bank fixes the list of key
 names at construction (``key_names[i]`` is filter ``i``), sizes every filter with
 ``Bloomfilter.optimal_m`` / ``optimal_k`` (bloomfilter.rb:25-28) and takes a mixed batch of
-``(key name, key)`` pairs in one launch.
+``(key name, key)`` pairs in one launch.  ``which`` / ``include_across`` ask the question only a
+bank can answer in one launch: which of the key names have seen this key.
 
 Redis sync follows ``drivers/hip.py``'s contract, per key name:
 
@@ -161,6 +162,21 @@ class BloomfilterBank:
 
     def include(self, name, key) -> bool:
         return bool(self.include_many([name], [key])[0])
+
+    # -- ruby.rb:20-30 of one key in many key names: the key is hashed once (bf_bank_include_across)
+    def include_across(self, keys: Iterable, names: Optional[Iterable] = None) -> np.ndarray:
+        """A bool array of shape (len(keys), len(names)): [j, i] = ``include(names[i], keys[j])``.
+        ``names`` defaults to every key name, in ``key_names`` order.  A read: Redis is not touched."""
+        self._expired()
+        ids = None if names is None else np.array([self._id(n) for n in names], np.uint32)
+        buf, offs = _keys.pack(list(keys))
+        return self.bank.include_across(buf, offs, ids)
+
+    def which(self, key, names: Optional[Iterable] = None) -> List[str]:
+        """The key names whose filter contains ``key``, in ``names`` order (default: ``key_names``)."""
+        listed = self.key_names if names is None else [str(n) for n in names]
+        hits = self.include_across([key], None if names is None else listed)[0]
+        return [n for n, hit in zip(listed, hits) if hit]
 
     # -- ruby.rb:33-35
     def clear(self, name=None) -> None:

@@ -14,6 +14,9 @@
 //   bank_keys_kernel    insert / include?: one lane per key, 256 keys per workgroup staged
 //                       through LDS (bfdev::for_key_tile), SHA-1 and the offsets of ruby.rb:41-55
 //                       from bf_device.h, the k probes inside the lane's own filter.
+//   bank_across_kernel  include? of one key in many filters: the same tile, hashed once per
+//                       workgroup, its k bit positions tested in every filter of a chunk of the
+//                       list; one 64-entry mask word per lane and group.
 //   bank_*_kernel       per-filter BITCOUNT, clear, gather-and-trim (export) and scatter
 //                       (import): a workgroup, or a wave when stride <= kWaveStrideBytes, owns
 //                       one listed filter, streams it in 16-byte vectors and reduces with
@@ -125,6 +128,125 @@ __global__ __launch_bounds__(kBankTile) void bank_keys_kernel(BfGeom g, uint64_t
                 if (out8) out8[j] = (uint8_t)flipped;
             }
         });
+}
+
+// ---- cross query: one key against many filters ----------------------------------------------
+
+// List entries a workgroup walks with one hashed key tile: one 64-entry mask word.  Every
+// (tile, chunk) workgroup hashes its tile again, so the length trades that SHA-1 against spread.
+// Measured at 64 / 128 / 256 (DESIGN.md 6h "Cross queries"; build with -DBFHIP_ACROSS_CHUNK=...
+// to repeat it): the SHA-1 is lost in the loads where there are many tiles and many chunks
+// (under 1 %), while a workgroup's time grows with its chunk where there are few tiles.  At 64
+// one key against 10^5 filters is 1,563 workgroups and 2^20 keys against 32 filters hash once.
+#ifndef BFHIP_ACROSS_CHUNK
+#define BFHIP_ACROSS_CHUNK 64
+#endif
+constexpr uint32_t kAcrossChunk = BFHIP_ACROSS_CHUNK;
+constexpr uint32_t kAcrossMaxY = 65535;   // the grid's y limit: beyond it a workgroup strides over chunks
+static_assert(kAcrossChunk % 64 == 0 && kAcrossChunk <= kBankTile, "whole mask words, staged by one pass of the workgroup");
+
+// mask word (j, e / 64) bit e % 64 = Ruby#include? (ruby.rb:20-30) of key j in the filter of
+// list entry e (ids == NULL: filter e).  A key's k offsets (ruby.rb:41-55) do not depend on the
+// filter, so the lane hashes once, keeps the first round's (word, shift) pairs in registers and
+// tests them at id * stride for every entry of its chunk; rounds past the first are recomputed
+// from the digest and reached only by a lane whose AND still holds.  One writer per mask word,
+// zeros included.  status as in bank_keys_kernel: a refused key's row and a refused entry's
+// column read 0.
+__global__ __launch_bounds__(kBankTile) void bank_across_kernel(BfGeom g, uint64_t n_filters, uint64_t stride_words,
+                                                                const uint8_t* __restrict__ keys16,
+                                                                const uint64_t* __restrict__ offsets, uint64_t bias,
+                                                                const uint32_t* __restrict__ ids, uint64_t count,
+                                                                uint64_t n, uint64_t row_words,
+                                                                unsigned long long* __restrict__ mask,
+                                                                uint32_t* __restrict__ status) {
+    __shared__ uint64_t s_off[kBankTile + 1];
+    __shared__ uint4 s_stage[kBankStageVec + kStageSlackVec];
+    __shared__ uint32_t s_ids[kAcrossChunk];
+    const uint64_t tile0 = (uint64_t)blockIdx.x * kBankTile;
+    const uint32_t cnt = (uint32_t)((n - tile0) < (uint64_t)kBankTile ? (n - tile0) : kBankTile);
+    const uint64_t nchunks = (count + kAcrossChunk - 1) / kAcrossChunk;
+    for (uint64_t chunk = blockIdx.y; chunk < nchunks; chunk += gridDim.y) {
+        const uint64_t e0 = chunk * kAcrossChunk;
+        const uint32_t len = (uint32_t)((count - e0) < (uint64_t)kAcrossChunk ? (count - e0) : kAcrossChunk);
+        // the chunk's ids, read once per workgroup; for_key_tile's first barrier publishes them
+        // and its last one frees s_ids for the next chunk
+        if (threadIdx.x < len) {
+            const uint64_t f = ids ? (uint64_t)ids[e0 + threadIdx.x] : e0 + threadIdx.x;
+            if (f >= n_filters) status[1] = 1u;
+            s_ids[threadIdx.x] = (uint32_t)f;
+        }
+        for_key_tile<kBankTile, kBankStageVec>(keys16, offsets, bias, tile0, cnt, s_off, s_stage, status,
+            [&](auto staged, uint32_t lane, const uint32_t* src, uint32_t s, uint32_t L) {
+                // a refused key arrives as the empty key (bank_keys_kernel): its row is zeros
+                const bool ok = key_ok(s_off[0], s_off[lane], s_off[lane + 1], s_off[cnt], nullptr);
+                uint32_t H[5];
+                sha1_any<decltype(staged)::value>(src, s, L, H);
+                const uint32_t k = g.k;
+                // the first round's (word, shift) pairs; a probe past k reads word 0 and is ORed
+                // away by pad, so a round's loads are issued without a branch between them
+                uint32_t w[kChunk], sh[kChunk], pad[kChunk];
+#pragma unroll
+                for (int c = 0; c < kChunk; ++c) {
+                    w[c] = 0; sh[c] = 0; pad[c] = 1u;
+                    if ((uint32_t)c < k) {
+                        const uint64_t o = probe_offset(g, H[0], H[1], H[2], H[3], (uint32_t)c);
+                        w[c] = (uint32_t)(o >> 5);   // < stride_words <= 2^32 (checked at create)
+                        sh[c] = (uint32_t)(o ^ 7u) & 31u;
+                        pad[c] = 0u;
+                    }
+                }
+                // One list entry in two steps, so that two entries' loads are in flight together.
+                // issue: the entry's filter (the id is the same in every lane: a scalar; a refused
+                // id reads filter 0 and answers 0) and the first round's loads.
+                auto issue = [&](uint32_t e, uint32_t (&v)[kChunk], uint32_t& live) -> const uint32_t* {
+                    const uint32_t id = __builtin_amdgcn_readfirstlane(s_ids[e]);
+                    live = (uint64_t)id < n_filters ? 1u : 0u;
+                    const uint32_t* fb = g.bits + (uint64_t)(live ? id : 0u) * stride_words;   // 64-bit word index
+#pragma unroll
+                    for (int c = 0; c < kChunk; ++c) v[c] = fb[w[c]];
+                    return fb;
+                };
+                // settle: the AND; with k > kChunk the later rounds, recomputed from the digest, for
+                // a lane whose AND still holds (ruby.rb:23's early exit)
+                auto settle = [&](const uint32_t* fb, const uint32_t (&v)[kChunk], uint32_t live) -> unsigned long long {
+                    uint32_t hit = live;
+#pragma unroll
+                    for (int c = 0; c < kChunk; ++c) hit &= (v[c] >> sh[c]) | pad[c];
+                    for (uint32_t i0 = kChunk; i0 < k && (hit & 1u); i0 += kChunk) {
+                        uint32_t v2[kChunk], s2[kChunk];
+#pragma unroll
+                        for (int c = 0; c < kChunk; ++c) {
+                            v2[c] = 0xFFFFFFFFu; s2[c] = 0;
+                            if (i0 + c < k) {
+                                const uint64_t o = probe_offset(g, H[0], H[1], H[2], H[3], i0 + c);
+                                s2[c] = (uint32_t)(o ^ 7u) & 31u;
+                                v2[c] = fb[o >> 5];
+                            }
+                        }
+#pragma unroll
+                        for (int c = 0; c < kChunk; ++c) hit &= v2[c] >> s2[c];
+                    }
+                    return hit & 1u;
+                };
+                unsigned long long* __restrict__ row = mask + (tile0 + lane) * row_words + (e0 >> 6);
+                for (uint32_t g0 = 0; g0 < len; g0 += 64) {
+                    const uint32_t ge = len - g0 < 64u ? len - g0 : 64u;
+                    unsigned long long acc = 0;
+                    if (ok) {
+                        uint32_t va[kChunk], vb[kChunk], la, lb;
+                        uint32_t i = 0;
+                        for (; i + 2 <= ge; i += 2) {
+                            const uint32_t* fa = issue(g0 + i, va, la);
+                            const uint32_t* fb = issue(g0 + i + 1, vb, lb);
+                            acc |= settle(fa, va, la) << i;
+                            acc |= settle(fb, vb, lb) << (i + 1);
+                        }
+                        if (i < ge) acc |= settle(issue(g0 + i, va, la), va, la) << i;
+                    }
+                    row[g0 >> 6] = acc;
+                }
+            });
+    }
 }
 
 // ---- per-filter kernels -------------------------------------------------------------------
@@ -474,6 +596,26 @@ int stage_list(bf_bank* b, const uint32_t* ids, uint64_t count, const uint32_t**
     return BF_OK;
 }
 
+// The staged mask of one chunk of a host cross query stays under this (a row longer than it goes alone).
+constexpr uint64_t kAcrossMaskCap = 64ull << 20;
+
+// Bytes of a mask row of count entries, 8 * ceil(count / 64).
+uint64_t across_row_bytes(uint64_t count) { return (count / 64 + (count % 64 ? 1 : 0)) * 8; }
+
+int launch_across(bf_bank* b, const uint8_t* d_keys, const uint64_t* d_off, uint64_t n, const uint32_t* d_ids,
+                  uint64_t count, uint8_t* d_mask, hipStream_t s) {
+    if (n >= (1ull << 31) * (uint64_t)kBankTile) return bank_err(b, BF_EINVAL, "n too large for one launch");
+    uint64_t bias = 0;
+    const uint8_t* k16 = align_keys(d_keys, &bias);
+    const uint64_t chunks = (count + kAcrossChunk - 1) / kAcrossChunk;
+    const dim3 grid((uint32_t)((n + kBankTile - 1) / kBankTile), (uint32_t)std::min<uint64_t>(chunks, kAcrossMaxY));
+    hipLaunchKernelGGL(bank_across_kernel, grid, dim3(kBankTile), 0, s, b->g, b->n_filters, b->stride / 4, k16, d_off,
+                       bias, d_ids, count, n, across_row_bytes(count) / 8, reinterpret_cast<unsigned long long*>(d_mask),
+                       b->d_status);
+    HIPCHK(b, hipGetLastError());
+    return BF_OK;
+}
+
 // ids == NULL clears every filter (one fill of the allocation; count is not read).
 int launch_clear(bf_bank* b, const uint32_t* d_ids, uint64_t count, hipStream_t s) {
     if (!d_ids) {
@@ -641,6 +783,80 @@ int bf_bank_insert_many_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64
 int bf_bank_include_many_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets,
                              const uint32_t* d_filter_ids, uint64_t n, uint8_t* d_out, void* stream) {
     return run_dev(b, BANK_INCLUDE, d_key_bytes, d_offsets, d_filter_ids, n, d_out, stream);
+}
+
+int bf_bank_across_row_bytes(uint64_t count, uint64_t* bytes) {
+    if (!bytes) return BF_EINVAL;
+    *bytes = across_row_bytes(count);
+    return BF_OK;
+}
+
+int bf_bank_include_across(bf_bank* b, const uint8_t* key_bytes, const uint64_t* offsets, uint64_t n,
+                           const uint32_t* ids, uint64_t count, uint8_t* mask) {
+    if (!b) return BF_EINVAL;
+    if (n == 0 || count == 0) return BF_OK;
+    CallScope cs(b);
+    if (!mask) return bank_err(b, BF_EINVAL, "mask is NULL");
+    if (!offsets || (!key_bytes && offsets[n] != offsets[0])) return bank_err(b, BF_EINVAL, "NULL keys / offsets");
+    const uint64_t lo = offsets[0], hi = offsets[n];
+    for (uint64_t j = 0; j < n; ++j)
+        if (!key_ok(lo, offsets[j], offsets[j + 1], hi, nullptr))
+            return bank_err(b, BF_EINVAL, "key %llu: offsets must be non-decreasing and every key below 2 GiB",
+                            (unsigned long long)j);
+    int rc = check_list(b, ids, count, true);
+    if (rc) return rc;
+    const uint64_t row = across_row_bytes(count);
+    uint64_t total = 0;
+    if (__builtin_mul_overflow(n, row, &total))
+        return bank_err(b, BF_EINVAL, "%llu mask rows of %llu bytes overflow a 64-bit byte size", (unsigned long long)n,
+                        (unsigned long long)row);
+    if (int orc = cs.open(b->stream)) return orc;
+    const uint32_t* d_ids = nullptr;
+    if ((rc = stage_list(b, ids, count, &d_ids))) return rc;
+    // run_host's chunks, bounded again so that the staged mask stays under kAcrossMaskCap
+    const uint64_t max_rows = std::max<uint64_t>(1, kAcrossMaskCap / row);
+    std::vector<uint64_t> rebased;
+    uint64_t a = 0;
+    while (a < n) {
+        uint64_t e = std::min<uint64_t>(n, a + std::min<uint64_t>(b->batch_keys, max_rows));
+        if (offsets[e] - offsets[a] > b->batch_bytes) {
+            e = (uint64_t)(std::upper_bound(offsets + a, offsets + e + 1, offsets[a] + b->batch_bytes) - offsets) - 1;
+            if (e <= a) e = a + 1;
+        }
+        const uint64_t cn = e - a, nbytes = offsets[e] - offsets[a];
+        if ((rc = ensure_keys_io(b, nbytes, cn))) return rc;
+        if ((rc = grow(b, (void**)&b->d_io, &b->io_cap, cn * row))) return rc;
+        rebased.resize(cn + 1);
+        for (uint64_t j = 0; j <= cn; ++j) rebased[j] = offsets[a + j] - offsets[a];
+        if (nbytes) HIPCHK(b, hipMemcpyAsync(b->d_keys, key_bytes + offsets[a], nbytes, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(b, hipMemsetAsync(b->d_keys + nbytes, 0, 16, b->stream));
+        HIPCHK(b, hipMemcpyAsync(b->d_off, rebased.data(), (cn + 1) * 8, hipMemcpyHostToDevice, b->stream));
+        if ((rc = launch_across(b, b->d_keys, b->d_off, cn, d_ids, count, b->d_io, b->stream))) return rc;
+        HIPCHK(b, hipMemcpyAsync(mask + a * row, b->d_io, cn * row, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(b, hipStreamSynchronize(b->stream));   // the staging buffers, `rebased` and `ids` are free again
+        a = e;
+    }
+    return BF_OK;
+}
+
+int bf_bank_include_across_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets, uint64_t n,
+                               const uint32_t* d_ids, uint64_t count, uint8_t* d_mask, void* stream) {
+    if (!b) return BF_EINVAL;
+    if (n == 0 || count == 0) return BF_OK;
+    CallScope cs(b);
+    if (!d_key_bytes || !d_offsets || !d_mask) return bank_err(b, BF_EINVAL, "NULL device pointer");
+    if ((reinterpret_cast<uintptr_t>(d_offsets) & 7u) || (reinterpret_cast<uintptr_t>(d_mask) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_ids) & 3u))
+        return bank_err(b, BF_EINVAL, "misaligned device pointer (d_offsets and d_mask: 8 bytes, d_ids: 4)");
+    int rc = check_list(b, d_ids, count, false);
+    if (rc) return rc;
+    uint64_t total = 0;
+    if (__builtin_mul_overflow(n, across_row_bytes(count), &total))
+        return bank_err(b, BF_EINVAL, "%llu mask rows of %llu bytes overflow a 64-bit byte size", (unsigned long long)n,
+                        (unsigned long long)across_row_bytes(count));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (int orc = cs.open(s)) return orc;
+    return launch_across(b, d_key_bytes, d_offsets, n, d_ids, count, d_mask, s);
 }
 
 int bf_bank_clear_dev(bf_bank* b, const uint32_t* d_ids, uint64_t count, void* stream) {

@@ -16,6 +16,16 @@ the median of --runs runs after --warmup.  Two baselines, timed the same way:
 One JSON line on stdout (and in --out).
 
     python tools/bench_bank.py [--filters 1000,100000] [--hashes 7] [--runs 25] [--out profiles/bank_ops.json]
+
+--across times the cross query instead (bf_bank_include_across_dev: one key against many
+filters, hashed once) against the only way there was before: the crossed batch through
+bf_bank_include_many_dev, every key repeated once per listed filter and the ids tiled, built on
+the device before timing.  Four shapes (ACROSS_SHAPES), filters half full (5,000 random keys
+each; the first query keys on top, each in one listed filter).  The two calls run alternately, HIP
+events around each, median / min / max of --runs runs after --warmup; the answers are compared
+once outside the timed region.
+
+    python tools/bench_bank.py --across [--hashes 7] [--runs 25] [--out profiles/bank_across.json]
 """
 import argparse
 import json
@@ -144,6 +154,100 @@ def run_bank(pkg, m, k, nf, n, buf, offs, runs, warmup) -> dict:
     return res
 
 
+# ---- --across: the cross query (bf_bank_include_across_dev) against the crossed batch ----------
+
+# (label, keys, listed filters or None for all, filters of the bank)
+ACROSS_SHAPES = [("2^20 keys x 32 of 10^3 filters", 1 << 20, 32, 1000),
+                 ("2^12 keys x all 10^3 filters", 1 << 12, None, 1000),
+                 ("64 keys x all 10^5 filters", 64, None, 100_000),
+                 # many tiles AND many list chunks: where hashing a tile again per chunk costs most
+                 ("2^16 keys x all 10^3 filters", 1 << 16, None, 1000)]
+FILL_PER_FILTER = SIZE // 2     # half full: 5,000 of the 10,000 keys a filter is sized for
+FILL_BATCH = 1 << 24
+
+
+def timed_pair(fns, runs: int, warmup: int):
+    """The functions run alternately, HIP events around each call on the null stream; per
+    function the sorted ms of the runs after the warm-up."""
+    ms = [[] for _ in fns]
+    for i in range(warmup + runs):
+        for which, fn in enumerate(fns):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if i >= warmup:
+                ms[which].append(e0.elapsed_time(e1))
+    return [sorted(x) for x in ms]
+
+
+def spread(ms, pairs: int) -> dict:
+    med = statistics.median(ms)
+    return {"ms": round(med, 4), "min_ms": round(ms[0], 4), "max_ms": round(ms[-1], 4),
+            "Gpairs_per_s": round(pairs / (med * 1e-3) / 1e9, 2)}
+
+
+def fill_half(bank, nf: int) -> None:
+    """FILL_PER_FILTER random 12-byte keys into every filter, generated on the device."""
+    total, gen = nf * FILL_PER_FILTER, torch.Generator(device="cuda").manual_seed(0xAC2055)
+    offs = torch.arange(FILL_BATCH + 1, dtype=torch.int64, device="cuda") * KEY_BYTES
+    for a in range(0, total, FILL_BATCH):
+        cn = min(FILL_BATCH, total - a)
+        keys = torch.randint(0, 256, (cn * KEY_BYTES + 16,), dtype=torch.uint8, device="cuda", generator=gen)
+        ids = (torch.arange(a, a + cn, dtype=torch.int64, device="cuda") % nf).to(torch.int32)
+        bank.insert_many_dev(keys.data_ptr(), offs.data_ptr(), ids.data_ptr(), cn, stream=0)
+        torch.cuda.synchronize()
+
+
+def run_across(pkg, m, k, label, n, listed, nf, runs, warmup) -> dict:
+    rng = np.random.default_rng([0xAC2055, n, nf])
+    ids = None if listed is None else rng.choice(nf, listed, replace=False).astype(np.uint32)
+    count = nf if ids is None else len(ids)
+    pairs = n * count
+    buf, offs = decimal_keys(n)
+    dk, do = to_dev(buf, offs)
+    # the crossed batch: key j once per list entry, the ids tiled, all on the device
+    d_listed = torch.arange(nf, dtype=torch.int32, device="cuda") if ids is None else \
+        torch.from_numpy(ids.view(np.int32).copy()).cuda()
+    xk = torch.cat([dk[:-16].view(n, KEY_BYTES).repeat_interleave(count, dim=0).reshape(-1), dk[-16:]])
+    xo = torch.arange(pairs + 1, dtype=torch.int64, device="cuda") * KEY_BYTES
+    xi = d_listed.repeat(n)
+    out8 = torch.zeros(pairs, dtype=torch.uint8, device="cuda")
+    res = {"shape": label, "keys": n, "listed": count, "n_filters": nf, "pairs": pairs}
+    with pkg.FilterBank(m, k, nf, device=0) as bank:
+        row = bank.across_row_bytes(count)
+        res["device_bytes"], res["mask_bytes"], res["crossed_key_bytes"] = bank.device_bytes, n * row, pairs * KEY_BYTES
+        mask = torch.full((n * row,), 0xFF, dtype=torch.uint8, device="cuda")
+        fill_half(bank, nf)
+        # the first query keys are members of one listed filter each (at most 16 more keys per
+        # filter), so both answers occur
+        members = min(n, 16 * count)
+        home = d_listed[torch.from_numpy(rng.integers(0, count, members)).cuda()]
+        bank.insert_many_dev(dk.data_ptr(), do.data_ptr(), home.data_ptr(), members, stream=0)
+        torch.cuda.synchronize()
+        d_ids = 0 if ids is None else d_listed.data_ptr()
+        t_across, t_crossed = timed_pair(
+            [lambda: bank.include_across_dev(dk.data_ptr(), do.data_ptr(), n, mask.data_ptr(), d_ids, count, stream=0),
+             lambda: bank.include_many_dev(xk.data_ptr(), xo.data_ptr(), xi.data_ptr(), pairs, out8.data_ptr(), stream=0)],
+            runs, warmup)
+        torch.cuda.synchronize()
+        bank.sync()
+        # the same answers, once, outside the timed region
+        shifts = torch.arange(8, dtype=torch.uint8, device="cuda")
+        bits = ((mask.view(n, row, 1) >> shifts) & 1).view(n, row * 8)
+        assert bool((bits[:, :count] == out8.view(n, count)).all()), "the cross query and the crossed batch differ"
+        assert not bool(bits[:, count:].any())
+        res["hits"] = int(out8.sum())
+        assert res["hits"] >= members
+    res["across"], res["crossed"] = spread(t_across, pairs), spread(t_crossed, pairs)
+    res["ratio"] = round(res["crossed"]["ms"] / res["across"]["ms"], 2)
+    res["ratio_min"] = round(t_crossed[0] / t_across[-1], 2)      # the baseline's fastest run over the query's slowest
+    res["ratio_max"] = round(t_crossed[-1] / t_across[0], 2)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--filters", default="1000,100000")
@@ -152,6 +256,8 @@ def main():
     ap.add_argument("--runs", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--across", action="store_true",
+                    help="time the cross query against the crossed batch instead (profiles/bank_across.json)")
     args = ap.parse_args()
     if args.runs < 20:
         ap.error("--runs must be at least 20 (the medians quoted in DESIGN.md)")
@@ -161,6 +267,16 @@ def main():
     torch.cuda.set_device(0)
     m = pkg.Bloomfilter.optimal_m(SIZE, ERROR_RATE)
     k = args.hashes or pkg.Bloomfilter.optimal_k(SIZE, m)
+    if args.across:
+        doc = {"tool": "tools/bench_bank.py --across", "device": torch.cuda.get_device_name(0), "m": m, "k": k,
+               "key_bytes": KEY_BYTES, "fill_per_filter": FILL_PER_FILTER, "runs": args.runs, "warmup": args.warmup,
+               "shapes": [run_across(pkg, m, k, *shape, args.runs, args.warmup) for shape in ACROSS_SHAPES]}
+        line = json.dumps(doc)
+        print(line)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     n = 1 << args.log2_keys
     buf, offs = decimal_keys(n)
     doc = {"tool": "tools/bench_bank.py", "device": torch.cuda.get_device_name(0), "m": m, "k": k, "keys": n,
