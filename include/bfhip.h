@@ -35,7 +35,8 @@
  *   bf_estimate_count  distinct keys behind a bit count, under the probe law of        ruby.rb:51
  *   bf_bank_*          many filters of one (m, k), one per key_name, behind one handle:
  *                      Ruby#insert / #include? / #clear per (key_name, key)     ruby.rb:15-35, 57-63
- *                      and #include? of one key in every listed key_name (bf_bank_include_across)
+ *                      and #include? of one key in every listed key_name (bf_bank_include_across);
+ *                      key_names combined with each other (bf_bank_fold, bf_bank_overlap)   ruby.rb:59, 61-62
  *   bf_optimal_m/_k    Redis::Bloomfilter.optimal_m / optimal_k       lib/redis/bloomfilter.rb:50-58
  *   bf_version         Redis::Bloomfilter.version                     lib/redis/bloomfilter/version.rb:6-8
  *
@@ -680,6 +681,50 @@ int  bf_lua_index(double entries, uint64_t count, uint32_t* layer);
  *                        (BF_IMPORT_OR).  A string bf_import_redis would refuse (longer than
  *                        ceil(m / 8) bytes, or a bit set at or past m) is BF_ERANGE, as there, and
  *                        nothing is imported.
+ *   bf_bank_fold         BITOP AND / OR over filters of the bank, every group of a call in ONE
+ *                        launch: a roll-up ("last 7 days" = the OR of seven daily key_names), an
+ *                        in-place merge, a copy, or only the count.  All filters share one layout
+ *                        (ruby.rb:59), so the strings combine byte for byte.  Group g's sources are
+ *                        src_ids[seg[g] .. seg[g + 1]) (seg: groups + 1 entries, seg[0] == 0,
+ *                        non-decreasing); its result is src[0] OP src[1] OP ...; a source may
+ *                        repeat.  With dst_ids, filter dst_ids[g] is REPLACED by the result; the
+ *                        destination may be among its own group's sources (dst |= ..., dst &= ...),
+ *                        and a group of one source is a copy.  changed[g] (nullable) = 1 iff the
+ *                        destination's bytes differ afterwards: the reference's "the string
+ *                        changed" (ruby.rb:61-62), which decides the write-back and the EXPIRE of
+ *                        that key_name; always 0 with dst_ids == NULL.  set_bits[g] (nullable) =
+ *                        BITCOUNT of the result.  dst_ids == NULL counts and writes no filter; only
+ *                        then is BF_BITOP_XOR allowed, as in bf_bitcount_op.  A destination's bytes
+ *                        from ceil(m_bits / 8) to stride stay zero, as its sources' are.  Every
+ *                        given changed / set_bits entry is written, so the caller does not clear
+ *                        them.  groups == 0: BF_OK, nothing written.  The host form refuses
+ *                        (BF_EINVAL, outputs and bank untouched) a NULL seg or src_ids, an unknown
+ *                        op, XOR with dst_ids, seg[0] != 0, a seg that decreases, an empty group
+ *                        (the AND of nothing is not a filter), an id >= n_filters, a destination
+ *                        that is also another group's destination, and a destination that another
+ *                        group reads (the result would depend on the order of the groups).  The
+ *                        _dev form (n_src = seg[groups]; it zeroes the outputs on the stream where
+ *                        its kernel sums into them) refuses NULL or misaligned pointers (d_seg,
+ *                        d_set_bits: 8 bytes; d_src_ids, d_dst_ids: 4), an unknown op and XOR with
+ *                        d_dst_ids; its kernel SKIPS a group that is empty, whose seg runs
+ *                        backwards or past n_src, or that names an id >= n_filters (destination
+ *                        untouched, changed and set_bits 0) and sets the status word (below).
+ *                        Destinations that alias another group's destination or source are not
+ *                        detected there: those filters' contents are then unspecified, nothing
+ *                        outside the bank is accessed.
+ *   bf_bank_overlap      out[i * cols + j] = BITCOUNT(filter row_ids[i] AND filter col_ids[j]),
+ *                        64-bit, for every pair of two lists in one launch: which of the bank's
+ *                        key_names overlap, and by how much.  With the diagonal (or
+ *                        bf_bank_bitcount) a caller has OR = |A| + |B| - AND, XOR and Jaccard.
+ *                        row_ids == NULL: every filter in order, rows must be n_filters; col_ids ==
+ *                        NULL: the row list, cols must be rows (the matrix is then symmetric).
+ *                        Ids may repeat and come in any order.  Every entry is written.  rows ==
+ *                        0 or cols == 0: BF_OK, nothing written.  The host form refuses (BF_EINVAL,
+ *                        out untouched) a NULL out, those two count rules, an id >= n_filters and
+ *                        rows * cols * 8 past 64 bits.  The _dev form refuses a NULL or misaligned
+ *                        pointer (d_out: 8 bytes; the lists: 4) and the count rules; its kernel
+ *                        answers zeros in the row or column of an id >= n_filters and sets the
+ *                        status word (below).
  *
  *      Refusals.  The host-pointer forms check first: bf_check_offsets' rule on the offsets and
  *      every filter id < n_filters; on failure nothing is launched, the call returns BF_EINVAL
@@ -723,6 +768,21 @@ int  bf_bank_export_filters(bf_bank* b, const uint32_t* ids /* nullable: all */,
                             uint8_t* buf /* count * stride bytes */, uint64_t* lens /* count */);
 int  bf_bank_import_filters(bf_bank* b, const uint32_t* ids /* nullable: all */, uint64_t count, const uint8_t* buf,
                             const uint64_t* lens, uint32_t mode /* BF_IMPORT_* */);
+/* groups folds in ONE launch.  Group g's sources are src_ids[seg[g] .. seg[g+1]). */
+int  bf_bank_fold(bf_bank* b, uint32_t op /* BF_BITOP_* */,
+                  const uint32_t* dst_ids /* groups; nullable: count only, nothing written */,
+                  const uint64_t* seg /* groups + 1, seg[0] == 0, non-decreasing */,
+                  const uint32_t* src_ids /* seg[groups] */, uint64_t groups,
+                  uint8_t* changed /* nullable, groups */, uint64_t* set_bits /* nullable, groups */);
+int  bf_bank_fold_dev(bf_bank* b, uint32_t op, const uint32_t* d_dst_ids, const uint64_t* d_seg,
+                      const uint32_t* d_src_ids, uint64_t groups, uint64_t n_src /* = seg[groups] */,
+                      uint8_t* d_changed, uint64_t* d_set_bits, void* stream);
+/* out[i * cols + j] = BITCOUNT(filter row_ids[i] AND filter col_ids[j]), 64-bit. */
+int  bf_bank_overlap(bf_bank* b, const uint32_t* row_ids /* nullable: every filter, rows == n_filters */,
+                     uint64_t rows, const uint32_t* col_ids /* nullable: the row list, cols == rows */,
+                     uint64_t cols, uint64_t* out /* rows * cols */);
+int  bf_bank_overlap_dev(bf_bank* b, const uint32_t* d_row_ids, uint64_t rows, const uint32_t* d_col_ids,
+                         uint64_t cols, uint64_t* d_out, void* stream);
 
 /* ---- one key's k offsets without a filter (Ruby#indexes_for, ruby.rb:41-55): computed
  *      by the same device kernel as bf_indexes_many, on the calling thread's current

@@ -178,6 +178,10 @@ SIGNATURES = {
     "bf_bank_bitcount_dev": (ctypes.c_int, [_vp, _vp, _u64, _vp, _vp]),
     "bf_bank_export_filters": (ctypes.c_int, [_vp, _vp, _u64, _vp, _vp]),
     "bf_bank_import_filters": (ctypes.c_int, [_vp, _vp, _u64, _vp, _vp, _u32]),
+    "bf_bank_fold": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "bf_bank_fold_dev": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "bf_bank_overlap": (ctypes.c_int, [_vp, _vp, _u64, _vp, _u64, _vp]),
+    "bf_bank_overlap_dev": (ctypes.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp]),
     "bf_optimal_m": (ctypes.c_int64, [ctypes.c_double, ctypes.c_double]),
     "bf_optimal_k": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
 }
@@ -992,7 +996,60 @@ class FilterBank(_Handle):
         _bank_check(self._lib.bf_bank_import_filters(self.handle, _ptr(a), count, _ptr(buf), _ptr(lens), int(mode)),
                     self._h)
 
+    # -- filters combined with each other
+    def fold(self, op, sources, dst_ids=None) -> Tuple[np.ndarray, np.ndarray]:
+        """One fold per entry of ``sources`` (a sequence of id sequences), all in one launch
+        (bf_bank_fold): result g = the AND / OR of the filters ``sources[g]``.  With ``dst_ids``
+        filter ``dst_ids[g]`` is replaced by it (the destination may be among its own sources: an
+        in-place merge; one source: a copy); without, nothing is written and 'xor' is allowed too.
+        Returns ``(changed, set_bits)``: whether each destination's bytes differ afterwards (bool,
+        all False without ``dst_ids``) and the BITCOUNT of each result (uint64)."""
+        groups = [self._ids(s) for s in sources]
+        seg = np.zeros(len(groups) + 1, np.uint64)
+        if groups:
+            np.cumsum([n for _, n in groups], out=seg[1:])
+        live = [a[:n] for a, n in groups if n]
+        src = np.concatenate(live) if live else np.zeros(1, np.uint32)
+        dst = None
+        if dst_ids is not None:
+            dst, count = self._ids(dst_ids)
+            if count != len(groups):
+                raise ArgumentError("%d destinations for %d groups" % (count, len(groups)))
+        n = len(groups)
+        changed, set_bits = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint64)
+        _bank_check(self._lib.bf_bank_fold(self.handle, _op(op), _ptr(dst), _ptr(seg), _ptr(src), n, _ptr(changed),
+                                           _ptr(set_bits)), self._h)
+        return changed[:n].astype(bool), set_bits[:n]
+
+    def overlap(self, row_ids=None, col_ids=None) -> np.ndarray:
+        """BITCOUNT(filter row_ids[i] AND filter col_ids[j]) for every pair (bf_bank_overlap): a
+        uint64 array of shape (rows, cols).  ``row_ids=None``: every filter; ``col_ids=None``: the
+        row list, a symmetric matrix whose diagonal is ``bitcount``."""
+        a, rows = self._ids(row_ids)
+        c, cols = (None, rows) if col_ids is None else self._ids(col_ids)
+        out = np.zeros((max(rows, 1), max(cols, 1)), np.uint64)
+        _bank_check(self._lib.bf_bank_overlap(self.handle, _ptr(a), rows, _ptr(c), cols, _ptr(out)), self._h)
+        return out if rows and cols else np.zeros((rows, cols), np.uint64)
+
     # -- device-resident API
+    def fold_dev(self, op, d_seg: int, d_src_ids: int, groups: int, n_src: int, d_dst_ids: int = 0,
+                 d_changed: int = 0, d_set_bits: int = 0, stream=None) -> None:
+        """``groups`` folds on ``stream`` (bf_bank_fold_dev): d_seg holds groups + 1 uint64 ending in
+        n_src, d_src_ids n_src uint32; d_dst_ids = 0 counts only; ``groups`` bytes are written at
+        d_changed and ``groups`` uint64 at d_set_bits (each may be 0)."""
+        _bank_check(self._lib.bf_bank_fold_dev(self.handle, _op(op), d_dst_ids or None, d_seg or None, d_src_ids or None,
+                                               int(groups), int(n_src), d_changed or None, d_set_bits or None,
+                                               self._s(stream)), self._h)
+
+    def overlap_dev(self, d_out: int, d_row_ids: int = 0, rows: Optional[int] = None, d_col_ids: int = 0,
+                    cols: Optional[int] = None, stream=None) -> None:
+        """The overlap matrix on ``stream`` (bf_bank_overlap_dev): rows * cols uint64 are written at
+        d_out (d_row_ids = 0: every filter, rows = n_filters; d_col_ids = 0: the row list)."""
+        rows = self.n_filters if rows is None else int(rows)
+        cols = rows if cols is None else int(cols)
+        _bank_check(self._lib.bf_bank_overlap_dev(self.handle, d_row_ids or None, rows, d_col_ids or None, cols,
+                                                  d_out or None, self._s(stream)), self._h)
+
     def insert_many_dev(self, d_keys: int, d_offsets: int, d_filter_ids: int, n: int, d_key_flipped: int = 0,
                         stream=None) -> None:
         _bank_check(self._lib.bf_bank_insert_many_dev(self.handle, d_keys, d_offsets, d_filter_ids, int(n),

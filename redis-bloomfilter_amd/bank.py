@@ -6,7 +6,9 @@ and an application keeps one per tenant, per day or per feed.  A bank fixes the 
 names at construction (``key_names[i]`` is filter ``i``), sizes every filter with
 ``Bloomfilter.optimal_m`` / ``optimal_k`` (bloomfilter.rb:25-28) and takes a mixed batch of
 ``(key name, key)`` pairs in one launch.  ``which`` / ``include_across`` ask the question only a
-bank can answer in one launch: which of the key names have seen this key.
+bank can answer in one launch: which of the key names have seen this key.  ``merge`` / ``rollup``
+/ ``union_size`` / ``intersection_size`` / ``overlap`` combine key names with each other on the
+device (bf_bank_fold, bf_bank_overlap).
 
 Redis sync follows ``drivers/hip.py``'s contract, per key name:
 
@@ -79,6 +81,7 @@ class BloomfilterBank:
         self.bank = FilterBank(self.options["bits"], self.options["hashes"], len(names), device=device)
         self._deadline: Dict[int, float] = {}
         self._dirty: Set[int] = set()    # manual sync: filters changed since the last flush
+        self._replaced: Set[int] = set()   # ... of those, a rollup replaced: flush DELetes them first
         self.redis = redis if redis is not None else fakeredis.current()   # bloomfilter.rb:30
         self.reload()
 
@@ -113,6 +116,7 @@ class BloomfilterBank:
         for i in due:
             del self._deadline[i]
             self._dirty.discard(i)
+            self._replaced.discard(i)
             if self.redis is not None and self.sync_mode == "write_through":
                 self.redis.delete(self.key_names[i])
 
@@ -186,6 +190,7 @@ class BloomfilterBank:
         for i in ids:
             self._deadline.pop(i, None)
             self._dirty.discard(i)
+            self._replaced.discard(i)
         if self.redis is not None:
             self.redis.delete(*[self.key_names[i] for i in ids])
 
@@ -204,14 +209,90 @@ class BloomfilterBank:
         m, k = self.options["bits"], self.options["hashes"]
         return np.array([estimate_count(m, k, int(x)) for x in self.count_bits()], np.float64)
 
+    # -- key names combined with each other (bf_bank_fold / bf_bank_overlap)
+    def _arm(self, i: int, expire, write: bool) -> None:
+        """``expire || default_expire`` for filter i, as ``insert_many`` arms a changed key name."""
+        expire = self._expire(expire)
+        if expire is not None and expire is not False:   # ruby.rb:62: 0 counts
+            self._deadline[i] = self._clock() + float(expire)
+            if write:
+                self.redis.expire(self.key_names[i], expire)
+
+    def merge(self, dst, sources: Iterable, expire=None) -> bool:
+        """``dst |= OR(sources)`` on the device (BITOP OR dst dst sources...); True iff dst's string
+        changed.  It is then written back (write-through; an OR only grows the string, so SETRANGE
+        dst 0 is right) or marked for ``flush``, and ``expire`` armed as by an insert that set a bit."""
+        self._expired()
+        d = self._id(dst)
+        changed = bool(self.bank.fold("or", [[d] + [self._id(n) for n in sources]], [d])[0][0])
+        if changed:
+            write = self.redis is not None and self.sync_mode == "write_through"
+            if write:
+                self._write([d])
+            else:
+                self._dirty.add(d)
+            self._arm(d, expire, write)
+        return changed
+
+    def rollup(self, dst, sources: Iterable, expire=None) -> bool:
+        """``dst = OR(sources)``, replacing it ("last 7 days" from seven daily key names); True iff
+        dst's string changed.  The string may shrink and SETRANGE never shrinks a key, so the key is
+        DELeted and written anew; its TTL goes with the DEL, as in ``clear``, and is armed again
+        when the result is non-empty."""
+        self._expired()
+        d = self._id(dst)
+        srcs = [self._id(n) for n in sources]
+        if not srcs:
+            raise ArgumentError("rollup needs at least one source key name")
+        changed, set_bits = self.bank.fold("or", [srcs], [d])
+        if changed[0]:
+            write = self.redis is not None and self.sync_mode == "write_through"
+            self._deadline.pop(d, None)
+            if write:
+                self.redis.delete(self.key_names[d])
+                self._write([d])
+            else:
+                self._dirty.add(d)
+                self._replaced.add(d)
+            if int(set_bits[0]):
+                self._arm(d, expire, write)
+        return bool(changed[0])
+
+    def union_size(self, names: Iterable) -> float:
+        """Estimated distinct keys of the listed key names together (``estimate_count`` of a
+        count-only OR); nothing is modified, Redis is not touched."""
+        self._expired()
+        _, set_bits = self.bank.fold("or", [[self._id(n) for n in names]])
+        return estimate_count(self.options["bits"], self.options["hashes"], int(set_bits[0]))
+
+    def intersection_size(self, a, b) -> float:
+        """Estimated keys two key names share, by inclusion-exclusion n(A) + n(B) - n(A or B)."""
+        self._expired()
+        ia, ib = self._id(a), self._id(b)
+        _, bits = self.bank.fold("or", [[ia], [ib], [ia, ib]])
+        na, nb, nu = (estimate_count(self.options["bits"], self.options["hashes"], int(x)) for x in bits)
+        return na + nb - nu
+
+    def overlap(self, names_a: Optional[Iterable] = None, names_b: Optional[Iterable] = None) -> np.ndarray:
+        """uint64 [i, j] = BITCOUNT(names_a[i] AND names_b[j]); ``names_a`` defaults to every key
+        name, ``names_b`` to ``names_a``.  A read: Redis is not touched."""
+        self._expired()
+        rows = None if names_a is None else np.array([self._id(n) for n in names_a], np.uint32)
+        cols = None if names_b is None else np.array([self._id(n) for n in names_b], np.uint32)
+        return self.bank.overlap(rows, cols)
+
     # -- Redis sync
     def flush(self, full: bool = False) -> int:
-        """Write the filters that changed since the last flush (``full``: every non-empty one)."""
+        """Write the filters that changed since the last flush (``full``: every non-empty one).  A
+        filter a ``rollup`` replaced is DELeted first: its string may have shrunk."""
         self._expired()
         ids = range(len(self.key_names)) if full else self._dirty
+        if self.redis is not None and self._replaced:
+            self.redis.delete(*[self.key_names[i] for i in sorted(self._replaced)])
         sent = self._write(list(ids))
         if self.redis is not None:
             self._dirty.clear()
+            self._replaced.clear()
         return sent
 
     def reload(self, names: Optional[Iterable] = None) -> None:
@@ -225,6 +306,7 @@ class BloomfilterBank:
             data = self.redis.get(self.key_names[i])
             self._deadline.pop(i, None)
             self._dirty.discard(i)
+            self._replaced.discard(i)
             if data is None:
                 gone.append(i)
                 continue

@@ -21,6 +21,13 @@
 //                       (import): a workgroup, or a wave when stride <= kWaveStrideBytes, owns
 //                       one listed filter, streams it in 16-byte vectors and reduces with
 //                       shuffles; one writer per output, no global atomics.
+//   bank_fold_kernel    BITOP AND / OR / XOR over groups of filters, every group of a call in one
+//                       launch: the same owners up to kFoldSliceStride, above it a 2-D grid of
+//                       stride slices x groups with one atomic add per workgroup.
+//   bank_overlap_kernel BITCOUNT(A AND B) for every pair of two lists: a tiled binary GEMM, 64 x
+//                       64 pairs per workgroup staged through LDS, the stride split over grid z
+//                       where the tiles are few.  bank_overlap_few_kernel streams at most 4 x 4
+//                       pairs of long filters without a tile.
 #include "bfhip.h"
 #include "bf_device.h"
 #include "bf_host.h"
@@ -423,6 +430,328 @@ uint32_t owned_grid(uint64_t stride, uint64_t count) {
     return g > kBankMaxBlocks ? kBankMaxBlocks : (g ? (uint32_t)g : 1u);
 }
 
+// ---- folds: filters of the bank combined with each other ------------------------------------
+
+// A stride above this is cut into slices over a 2-D grid (slices x groups); up to it one owner
+// (bank_owner) takes a whole group.  Measured (DESIGN.md 6h "Folds"; build with
+// -DBFHIP_FOLD_SLICE_STRIDE=... to repeat it).
+#ifndef BFHIP_FOLD_SLICE_STRIDE
+#define BFHIP_FOLD_SLICE_STRIDE (64u << 10)
+#endif
+constexpr uint64_t kFoldSliceStride = BFHIP_FOLD_SLICE_STRIDE;
+constexpr uint32_t kFoldUnroll = 4;                          // vectors a lane folds side by side
+constexpr uint32_t kFoldSliceVec = kBankLanes * kFoldUnroll; // vectors of one workgroup's slice: 16 KiB
+constexpr uint64_t kFoldMaxBlocks = 1ull << 22;              // the slice grid: groups stride beyond this
+constexpr uint64_t kFoldMaxSlices = 1024;                    // workgroups of one group: 4 a CU
+static_assert(kFoldSliceStride >= kWaveStrideBytes, "the slice grid is a workgroup's");
+
+template <uint32_t OP>
+__device__ __forceinline__ uint4 fold_op(const uint4& a, const uint4& b) {
+    if constexpr (OP == BF_BITOP_AND) return make_uint4(a.x & b.x, a.y & b.y, a.z & b.z, a.w & b.w);
+    else if constexpr (OP == BF_BITOP_OR) return make_uint4(a.x | b.x, a.y | b.y, a.z | b.z, a.w | b.w);
+    else return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w);
+}
+
+// Group g = src[seg[g]] OP src[seg[g] + 1] OP ... (ruby.rb:59's strings, combined bit for bit as
+// BITOP does).  WRITE: the result replaces filter dst_ids[g], a vector stored only where it
+// differs (changed[g], ruby.rb:61-62's "the string changed"); set_bits[g] = BITCOUNT of the result.
+// A lane reads its vector of every source and of the destination before it stores that vector
+// and no other lane touches it, so the destination may be one of its own group's sources.
+// `bits` is read and written through one pointer: no __restrict__.
+//
+// Up to kFoldSliceStride an owner takes a group (grid x: groups); one writer per output.  Above
+// it grid x cuts the stride into slices of kFoldSliceVec vectors (at most kFoldMaxSlices workgroups
+// a group, each striding over the slices: atomics on one address serialise) and grid y walks the
+// groups; each workgroup adds its slices' count into set_bits[g] and raises changed[g], both zeroed
+// on the stream by the caller (every raiser stores the same 1, so the byte needs no atomic).
+// A group that is empty, whose seg runs backwards or past n_src, or that names an id >=
+// n_filters is skipped (destination untouched, outputs 0) and sets status[1].
+template <uint32_t OP, bool WRITE>
+__global__ __launch_bounds__(kBankLanes) void bank_fold_kernel(uint4* bits, uint64_t stride_vec, uint64_t n_filters,
+                                                               const uint32_t* __restrict__ dst_ids,
+                                                               const unsigned long long* __restrict__ seg,
+                                                               const uint32_t* __restrict__ src_ids, uint64_t groups,
+                                                               uint64_t n_src, uint8_t* __restrict__ changed,
+                                                               unsigned long long* __restrict__ set_bits,
+                                                               uint32_t* __restrict__ status) {
+    __shared__ unsigned long long s_part[kBankLanes / 64];
+    const bool sliced = stride_vec * 16 > kFoldSliceStride;
+    const Owner o = bank_owner(stride_vec);
+    const uint32_t per = o.wave ? kBankLanes / 64 : 1u;
+    // a slice is one pass of the workgroup's lanes; workgroup x takes slices x, x + gridDim.x, ...
+    const uint64_t v0 = sliced ? (uint64_t)blockIdx.x * kFoldSliceVec : 0, v1 = stride_vec;
+    const uint64_t vstep = sliced ? (uint64_t)gridDim.x * kFoldSliceVec : (uint64_t)o.lanes * kFoldUnroll;
+    const uint64_t first = sliced ? blockIdx.y : (uint64_t)blockIdx.x * per;
+    const uint64_t step = sliced ? gridDim.y : (uint64_t)gridDim.x * per;
+    for (uint64_t base = first; base < groups; base += step) {
+        const uint64_t g = base + (o.wave ? (threadIdx.x >> 6) : 0u);
+        const bool live = g < groups;
+        uint64_t lo = 0, hi = 0;
+        unsigned long long bad = 0;
+        if (live) {
+            lo = seg[g];
+            hi = seg[g + 1];
+            if (!(lo < hi && hi <= n_src)) {
+                bad = 1;
+                hi = lo;   // nothing of src_ids is read
+            }
+            for (uint64_t s = lo + o.lane; s < hi; s += o.lanes)
+                if ((uint64_t)src_ids[s] >= n_filters) bad = 1;
+            if (WRITE && (uint64_t)dst_ids[g] >= n_filters) bad = 1;
+        }
+        bad = owner_reduce<true>(bad, o, s_part);
+        unsigned long long pop = 0, chg = 0;
+        if (live && !bad) {
+            uint4* d = WRITE ? bits + (uint64_t)dst_ids[g] * stride_vec : nullptr;
+            for (uint64_t vb = v0 + o.lane; vb < v1; vb += vstep) {
+                uint4 acc[kFoldUnroll];
+                const uint4* p = bits + (uint64_t)src_ids[lo] * stride_vec;
+#pragma unroll
+                for (uint32_t u = 0; u < kFoldUnroll; ++u) {
+                    const uint64_t v = vb + (uint64_t)u * o.lanes;
+                    acc[u] = v < v1 ? p[v] : make_uint4(0u, 0u, 0u, 0u);
+                }
+                for (uint64_t s = lo + 1; s < hi; ++s) {
+                    p = bits + (uint64_t)src_ids[s] * stride_vec;
+#pragma unroll
+                    for (uint32_t u = 0; u < kFoldUnroll; ++u) {
+                        const uint64_t v = vb + (uint64_t)u * o.lanes;
+                        if (v < v1) acc[u] = fold_op<OP>(acc[u], p[v]);
+                    }
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < kFoldUnroll; ++u) {
+                    const uint64_t v = vb + (uint64_t)u * o.lanes;
+                    if (v >= v1) continue;
+                    pop += popc4(acc[u]);
+                    if constexpr (WRITE) {
+                        const uint4 old = d[v];
+                        if ((old.x ^ acc[u].x) | (old.y ^ acc[u].y) | (old.z ^ acc[u].z) | (old.w ^ acc[u].w)) {
+                            d[v] = acc[u];
+                            chg = 1;
+                        }
+                    }
+                }
+            }
+        }
+        pop = owner_reduce<false>(pop, o, s_part);
+        if (WRITE) chg = owner_reduce<true>(chg, o, s_part);
+        if (live && o.lane == 0) {
+            if (bad) status[1] = 1u;
+            if (sliced) {
+                if (set_bits && pop) atomicAdd(set_bits + g, pop);
+                if (changed && chg) changed[g] = 1;
+            } else {
+                if (set_bits) set_bits[g] = pop;
+                if (changed) changed[g] = (uint8_t)chg;
+            }
+        }
+    }
+}
+
+// ---- overlap matrix: BITCOUNT(row filter AND column filter) for every pair --------------------
+
+// The binary analogue of a tiled GEMM, C[i][j] = sum over words of popc(A[i][w] & B[j][w]).  A
+// workgroup owns kOvTile x kOvTile pairs and walks its slice of the stride in chunks of
+// kOvChunkVec vectors per filter, staged through LDS (16-byte loads, ds_write_b128); every staged
+// word is then used by the tile's 64 filters of the other side.  Lane (ty, tx) = (lane / 16,
+// lane % 16) keeps the 4 x 4 pairs of rows ty + 16 i and columns tx + 16 j.
+//
+// LDS: a filter's chunk is a row of kOvPitchVec = 17 vectors (68 words).  The 16 lanes one
+// ds_read_b128 group serves hold every tx and at most two ty: the column rows tx * 68 words
+// start at bank 4 tx mod 64, sixteen disjoint runs of 4 banks, and the row-side address is a
+// broadcast per ty, two runs 4 banks apart.  The stage's ds_write_b128 groups of 8 lanes write 32
+// consecutive words.
+constexpr uint32_t kOvTile = 64;
+constexpr uint32_t kOvBlock = 4;
+constexpr uint32_t kOvChunkVec = 16;
+constexpr uint32_t kOvPitchVec = kOvChunkVec + 1;
+constexpr uint64_t kOvMaxSliceVec = 1ull << 24;   // 2^31 bits a slice: a pair's 32-bit count cannot overflow
+constexpr uint64_t kOvFill = 1024;                // workgroups wanted before the stride stops being split
+constexpr uint64_t kOvMinChunks = 8;              // chunks a slice keeps at least (2 KiB per filter)
+constexpr uint32_t kOvMaxGrid = 2048;             // tiles per grid dimension; a workgroup strides beyond
+static_assert(kOvTile == 16 * kOvBlock && kBankLanes == 256 && 2 * kOvTile * kOvChunkVec == 8 * kBankLanes,
+              "16 x 16 lanes, 4 x 4 pairs each, 8 staged vectors per lane and chunk");
+
+// One staged chunk's share of a lane's counters: rows ty + 16 i, columns tx + 16 j.  NI x NJ live
+// register blocks compiled in (the full tile and the two small squares), or 0: ni x nj at run
+// time, a uniform branch per block.
+template <uint32_t NI, uint32_t NJ>
+__device__ __forceinline__ void ov_chunk(const uint4* s_ab, uint32_t ty, uint32_t tx, uint32_t ni, uint32_t nj,
+                                         uint32_t (&acc)[kOvBlock][kOvBlock]) {
+    constexpr uint32_t CI = NI ? NI : kOvBlock, CJ = NJ ? NJ : kOvBlock;
+#pragma unroll 2
+    for (uint32_t vv = 0; vv < kOvChunkVec; ++vv) {
+        uint4 a[CI], b[CJ];
+#pragma unroll
+        for (uint32_t i = 0; i < CI; ++i)
+            if (NI || i < ni) a[i] = s_ab[(ty + 16 * i) * kOvPitchVec + vv];
+#pragma unroll
+        for (uint32_t j = 0; j < CJ; ++j)
+            if (NJ || j < nj) b[j] = s_ab[(kOvTile + tx + 16 * j) * kOvPitchVec + vv];
+#pragma unroll
+        for (uint32_t i = 0; i < CI; ++i)
+#pragma unroll
+            for (uint32_t j = 0; j < CJ; ++j)
+                if ((NI || i < ni) && (NJ || j < nj))
+                    acc[i][j] += __builtin_popcount(a[i].x & b[j].x) + __builtin_popcount(a[i].y & b[j].y) +
+                                 __builtin_popcount(a[i].z & b[j].z) + __builtin_popcount(a[i].w & b[j].w);
+    }
+}
+
+// out[(r * cols + c)] = BITCOUNT(filter of row r AND filter of column c); row r is filter
+// row_ids[r] (NULL: row0 + r), column c is col_ids[c] (NULL: c).  sym: the column list IS the row
+// list (cols == rows), the tiles strictly below the diagonal are skipped and mirrored from above.
+// add: gridDim.z > 1, the caller zeroed out and every slice adds its part (64-bit atomics; integer
+// sums are exact in any order); otherwise one writer per entry, zeros included.  A row or column
+// whose id is >= n_filters reads as the empty filter and sets status[1].
+__global__ __launch_bounds__(kBankLanes) void bank_overlap_kernel(const uint4* __restrict__ bits, uint64_t stride_vec,
+                                                                  uint64_t n_filters,
+                                                                  const uint32_t* __restrict__ row_ids, uint64_t row0,
+                                                                  uint64_t rows, const uint32_t* __restrict__ col_ids,
+                                                                  uint64_t cols, uint32_t sym, uint64_t slice_vec,
+                                                                  uint32_t add, unsigned long long* __restrict__ out,
+                                                                  uint32_t* __restrict__ status) {
+    __shared__ uint4 s_ab[2 * kOvTile * kOvPitchVec];   // [row side | column side]
+    __shared__ uint64_t s_f[2 * kOvTile];               // the tile's filters, ~0: none
+    const uint32_t tid = threadIdx.x, ty = tid >> 4, tx = tid & 15u;
+    const uint64_t row_tiles = (rows + kOvTile - 1) / kOvTile, col_tiles = (cols + kOvTile - 1) / kOvTile;
+    const uint64_t z0 = (uint64_t)blockIdx.z * slice_vec;
+    const uint64_t z1 = z0 + slice_vec < stride_vec ? z0 + slice_vec : stride_vec;
+    for (uint64_t ti = blockIdx.y; ti < row_tiles; ti += gridDim.y) {
+        for (uint64_t tj = blockIdx.x; tj < col_tiles; tj += gridDim.x) {
+            if (sym && tj < ti) continue;
+            const uint64_t r0 = ti * kOvTile, c0 = tj * kOvTile;
+            const uint32_t nr = (uint32_t)(rows - r0 < kOvTile ? rows - r0 : kOvTile);
+            const uint32_t nc = (uint32_t)(cols - c0 < kOvTile ? cols - c0 : kOvTile);
+            const uint32_t ni = (nr + 15u) / 16u, nj = (nc + 15u) / 16u;   // live register-block rows / columns
+            __syncthreads();   // the previous tile's s_f is read no more
+            if (tid < 2 * kOvTile) {
+                const bool col = tid >= kOvTile;
+                const uint32_t t = col ? tid - kOvTile : tid;
+                uint64_t f = ~0ull;
+                if (t < (col ? nc : nr)) {
+                    f = col ? (col_ids ? (uint64_t)col_ids[c0 + t] : c0 + t)
+                            : (row_ids ? (uint64_t)row_ids[r0 + t] : row0 + r0 + t);
+                    if (f >= n_filters) {
+                        status[1] = 1u;
+                        f = ~0ull;
+                    }
+                }
+                s_f[tid] = f;
+            }
+            __syncthreads();
+            uint32_t acc[kOvBlock][kOvBlock];
+#pragma unroll
+            for (uint32_t i = 0; i < kOvBlock; ++i)
+#pragma unroll
+                for (uint32_t j = 0; j < kOvBlock; ++j) acc[i][j] = 0;
+            for (uint64_t v0 = z0; v0 < z1; v0 += kOvChunkVec) {
+                // stage: pass `it` brings 16 filters (it < 4: rows 16 it.., else columns), 16 lanes a filter
+                uint4 x[8];
+#pragma unroll
+                for (uint32_t it = 0; it < 8; ++it) {
+                    x[it] = make_uint4(0u, 0u, 0u, 0u);
+                    if (it < kOvBlock ? it >= ni : it - kOvBlock >= nj) continue;
+                    const uint64_t f = s_f[it * 16 + ty];
+                    if (f != ~0ull && v0 + tx < z1) x[it] = bits[f * stride_vec + v0 + tx];
+                }
+#pragma unroll
+                for (uint32_t it = 0; it < 8; ++it) {
+                    if (it < kOvBlock ? it >= ni : it - kOvBlock >= nj) continue;
+                    s_ab[(it * 16 + ty) * kOvPitchVec + tx] = x[it];
+                }
+                __syncthreads();
+                if (ni == kOvBlock && nj == kOvBlock) ov_chunk<kOvBlock, kOvBlock>(s_ab, ty, tx, ni, nj, acc);
+                else if (ni == 2 && nj == 2) ov_chunk<2, 2>(s_ab, ty, tx, ni, nj, acc);
+                else if (ni == 1 && nj == 1) ov_chunk<1, 1>(s_ab, ty, tx, ni, nj, acc);
+                else ov_chunk<0, 0>(s_ab, ty, tx, ni, nj, acc);
+                __syncthreads();
+            }
+            const bool mirror = sym && tj != ti;
+#pragma unroll
+            for (uint32_t i = 0; i < kOvBlock; ++i)
+#pragma unroll
+                for (uint32_t j = 0; j < kOvBlock; ++j) {
+                    const uint32_t lr = ty + 16 * i, lc = tx + 16 * j;
+                    if (i >= ni || j >= nj || lr >= nr || lc >= nc) continue;
+                    const uint64_t r = r0 + lr, c = c0 + lc;
+                    const unsigned long long val = acc[i][j];
+                    if (add) {
+                        if (val) {
+                            atomicAdd(out + r * cols + c, val);
+                            if (mirror) atomicAdd(out + c * cols + r, val);
+                        }
+                    } else {
+                        out[r * cols + c] = val;
+                        if (mirror) out[c * cols + r] = val;
+                    }
+                }
+        }
+    }
+}
+
+// At most kOvFew x kOvFew pairs of long filters: a tile's slices would keep only a few hundred
+// bytes per filter in flight between two barriers, so the pairs are streamed instead, as the
+// fold's slice grid streams its sources.  At most kOvFewBlocks workgroups stride over the vectors
+// (every one ends in an atomic per pair on the same few addresses, which serialise); a lane loads
+// its vector of every listed filter, counts the up to 16 ANDs and the workgroup adds each pair's
+// sum into the zeroed out[] with one 64-bit atomic.  Ids as in bank_overlap_kernel
+// (NULL: row r is filter r, column c filter c).
+constexpr uint32_t kOvFew = 4;
+constexpr uint64_t kOvFewBlocks = 512;
+
+__global__ __launch_bounds__(kBankLanes) void bank_overlap_few_kernel(const uint4* __restrict__ bits, uint64_t stride_vec,
+                                                                      uint64_t n_filters,
+                                                                      const uint32_t* __restrict__ row_ids, uint32_t rows,
+                                                                      const uint32_t* __restrict__ col_ids, uint32_t cols,
+                                                                      unsigned long long* __restrict__ out,
+                                                                      uint32_t* __restrict__ status) {
+    __shared__ unsigned long long s_part[kBankLanes / 64];
+    uint64_t fr[kOvFew], fc[kOvFew];   // ~0: no such row / column, or a refused id
+#pragma unroll
+    for (uint32_t i = 0; i < kOvFew; ++i) {
+        fr[i] = i < rows ? (row_ids ? (uint64_t)row_ids[i] : i) : ~0ull;
+        fc[i] = i < cols ? (col_ids ? (uint64_t)col_ids[i] : i) : ~0ull;
+        if ((i < rows && fr[i] >= n_filters) || (i < cols && fc[i] >= n_filters)) status[1] = 1u;
+        if (fr[i] >= n_filters) fr[i] = ~0ull;
+        if (fc[i] >= n_filters) fc[i] = ~0ull;
+    }
+    uint32_t acc[kOvFew][kOvFew];   // a lane sees at most 2^30 / 256 vectors of 128 bits: no overflow
+#pragma unroll
+    for (uint32_t i = 0; i < kOvFew; ++i)
+#pragma unroll
+        for (uint32_t j = 0; j < kOvFew; ++j) acc[i][j] = 0;
+#pragma unroll 2
+    for (uint64_t v = (uint64_t)blockIdx.x * kBankLanes + threadIdx.x; v < stride_vec; v += (uint64_t)gridDim.x * kBankLanes) {
+        uint4 a[kOvFew], b[kOvFew];
+#pragma unroll
+        for (uint32_t i = 0; i < kOvFew; ++i) {
+            a[i] = fr[i] != ~0ull ? bits[fr[i] * stride_vec + v] : make_uint4(0u, 0u, 0u, 0u);
+            b[i] = fc[i] != ~0ull ? bits[fc[i] * stride_vec + v] : make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < kOvFew; ++i)
+#pragma unroll
+            for (uint32_t j = 0; j < kOvFew; ++j)
+                if (i < rows && j < cols)   // uniform
+                    acc[i][j] += __builtin_popcount(a[i].x & b[j].x) + __builtin_popcount(a[i].y & b[j].y) +
+                                 __builtin_popcount(a[i].z & b[j].z) + __builtin_popcount(a[i].w & b[j].w);
+    }
+    Owner o;
+    o.wave = false;
+    o.lane = threadIdx.x;
+    o.lanes = kBankLanes;
+#pragma unroll
+    for (uint32_t i = 0; i < kOvFew; ++i)
+#pragma unroll
+        for (uint32_t j = 0; j < kOvFew; ++j) {
+            if (i >= rows || j >= cols) continue;   // uniform
+            const unsigned long long sum = owner_reduce<false>(acc[i][j], o, s_part);
+            if (threadIdx.x == 0 && sum) atomicAdd(out + (uint64_t)i * cols + j, sum);
+        }
+}
+
 }  // namespace
 
 struct bf_bank : BfHostCore {   // mutex, device, stream, error, stream order: bf_host.h (the profile state idle)
@@ -628,6 +957,97 @@ int launch_clear(bf_bank* b, const uint32_t* d_ids, uint64_t count, hipStream_t 
     HIPCHK(b, hipGetLastError());
     return BF_OK;
 }
+
+// What both fold forms refuse without reading a list.
+int check_fold_op(bf_bank* b, uint32_t op, bool has_dst) {
+    if (op != BF_BITOP_AND && op != BF_BITOP_OR && op != BF_BITOP_XOR) return bank_err(b, BF_EINVAL, "unknown op %u", op);
+    if (op == BF_BITOP_XOR && has_dst)
+        return bank_err(b, BF_EINVAL, "BF_BITOP_XOR only counts: dst_ids must be NULL (a parity is not a filter)");
+    return BF_OK;
+}
+
+// One launch for every group.  The slice regime adds into the outputs, which are zeroed here.
+int launch_fold(bf_bank* b, uint32_t op, const uint32_t* d_dst, const uint64_t* d_seg, const uint32_t* d_src,
+                uint64_t groups, uint64_t n_src, uint8_t* d_changed, uint64_t* d_set_bits, hipStream_t s) {
+    const uint64_t stride_vec = b->stride / 16;
+    dim3 grid(owned_grid(b->stride, groups));
+    if (b->stride > kFoldSliceStride) {
+        const uint64_t slices = std::min<uint64_t>((stride_vec + kFoldSliceVec - 1) / kFoldSliceVec, kFoldMaxSlices);
+        const uint64_t gy = std::min<uint64_t>(std::min<uint64_t>(groups, 65535), std::max<uint64_t>(1, kFoldMaxBlocks / slices));
+        grid = dim3((uint32_t)slices, (uint32_t)gy);
+        if (d_set_bits) HIPCHK(b, hipMemsetAsync(d_set_bits, 0, groups * 8, s));
+        if (d_changed) HIPCHK(b, hipMemsetAsync(d_changed, 0, groups, s));
+    } else if (d_changed && !d_dst) {
+        HIPCHK(b, hipMemsetAsync(d_changed, 0, groups, s));   // a count-only fold changes nothing
+    }
+    uint4* bits = reinterpret_cast<uint4*>(b->g.bits);
+    const unsigned long long* seg = reinterpret_cast<const unsigned long long*>(d_seg);
+    unsigned long long* sb = reinterpret_cast<unsigned long long*>(d_set_bits);
+#define BF_FOLD_LAUNCH(OP, WRITE)                                                                                      \
+    hipLaunchKernelGGL((bank_fold_kernel<OP, WRITE>), grid, dim3(kBankLanes), 0, s, bits, stride_vec, b->n_filters,    \
+                       d_dst, seg, d_src, groups, n_src, (WRITE) ? d_changed : nullptr, sb, b->d_status)
+    if (op == BF_BITOP_XOR) BF_FOLD_LAUNCH(BF_BITOP_XOR, false);
+    else if (op == BF_BITOP_AND && d_dst) BF_FOLD_LAUNCH(BF_BITOP_AND, true);
+    else if (op == BF_BITOP_AND) BF_FOLD_LAUNCH(BF_BITOP_AND, false);
+    else if (d_dst) BF_FOLD_LAUNCH(BF_BITOP_OR, true);
+    else BF_FOLD_LAUNCH(BF_BITOP_OR, false);
+#undef BF_FOLD_LAUNCH
+    HIPCHK(b, hipGetLastError());
+    return BF_OK;
+}
+
+// The list rules both overlap forms share; *out_bytes = rows * cols * 8.
+int check_overlap(bf_bank* b, const uint32_t* row_ids, uint64_t rows, const uint32_t* col_ids, uint64_t cols,
+                  uint64_t* out_bytes) {
+    if (!row_ids && rows != b->n_filters)
+        return bank_err(b, BF_EINVAL, "row_ids == NULL lists every filter: rows must be n_filters = %llu, got %llu",
+                        (unsigned long long)b->n_filters, (unsigned long long)rows);
+    if (!col_ids && cols != rows)
+        return bank_err(b, BF_EINVAL, "col_ids == NULL is the row list: cols must be rows = %llu, got %llu",
+                        (unsigned long long)rows, (unsigned long long)cols);
+    uint64_t pairs = 0;
+    if (__builtin_mul_overflow(rows, cols, &pairs) || __builtin_mul_overflow(pairs, (uint64_t)8, out_bytes))
+        return bank_err(b, BF_EINVAL, "%llu x %llu counts overflow a 64-bit byte size", (unsigned long long)rows,
+                        (unsigned long long)cols);
+    return BF_OK;
+}
+
+// rows x cols counts at d_out.  d_rows == NULL: row r is filter row0 + r; d_cols == NULL: column
+// c is filter c.  sym: the column list is the row list, the lower tiles are mirrored.
+int launch_overlap(bf_bank* b, const uint32_t* d_rows, uint64_t row0, uint64_t rows, const uint32_t* d_cols,
+                   uint64_t cols, bool sym, uint64_t* d_out, hipStream_t s) {
+    const uint64_t stride_vec = b->stride / 16;
+    if (rows <= kOvFew && cols <= kOvFew && row0 == 0 && b->stride > kFoldSliceStride) {
+        // a handful of long filters: streamed pair by pair, every slice adding into the zeroed counts
+        HIPCHK(b, hipMemsetAsync(d_out, 0, rows * cols * 8, s));
+        hipLaunchKernelGGL(bank_overlap_few_kernel, dim3((uint32_t)std::min<uint64_t>((stride_vec + kBankLanes - 1) / kBankLanes, kOvFewBlocks)),
+                           dim3(kBankLanes), 0, s, reinterpret_cast<const uint4*>(b->g.bits), stride_vec, b->n_filters,
+                           d_rows, (uint32_t)rows, d_cols, (uint32_t)cols, reinterpret_cast<unsigned long long*>(d_out),
+                           b->d_status);
+        HIPCHK(b, hipGetLastError());
+        return BF_OK;
+    }
+    const uint64_t rt = (rows + kOvTile - 1) / kOvTile, ct = (cols + kOvTile - 1) / kOvTile;
+    const uint64_t chunks = (stride_vec + kOvChunkVec - 1) / kOvChunkVec;
+    // few tiles and a long stride: split it until about kOvFill workgroups run, a slice keeping
+    // kOvMinChunks chunks at least and kOvMaxSliceVec vectors at most
+    const uint64_t gx = std::min<uint64_t>(ct, kOvMaxGrid), gy = std::min<uint64_t>(rt, kOvMaxGrid);
+    const uint64_t tiles = sym ? gx * (gy + 1) / 2 : gx * gy;
+    uint64_t nz = std::min<uint64_t>((kOvFill + tiles - 1) / tiles, std::max<uint64_t>(1, chunks / kOvMinChunks));
+    nz = std::max<uint64_t>(nz, (stride_vec + kOvMaxSliceVec - 1) / kOvMaxSliceVec);
+    const uint64_t per = (chunks + nz - 1) / nz;
+    nz = (chunks + per - 1) / per;
+    if (nz > 1) HIPCHK(b, hipMemsetAsync(d_out, 0, rows * cols * 8, s));
+    hipLaunchKernelGGL(bank_overlap_kernel, dim3((uint32_t)gx, (uint32_t)gy, (uint32_t)nz), dim3(kBankLanes), 0, s,
+                       reinterpret_cast<const uint4*>(b->g.bits), stride_vec, b->n_filters, d_rows, row0, rows, d_cols,
+                       cols, sym ? 1u : 0u, per * kOvChunkVec, nz > 1 ? 1u : 0u,
+                       reinterpret_cast<unsigned long long*>(d_out), b->d_status);
+    HIPCHK(b, hipGetLastError());
+    return BF_OK;
+}
+
+// The staged counts of one chunk of a host overlap stay under this (a row longer than it goes alone).
+constexpr uint64_t kOverlapOutCap = 64ull << 20;
 
 }  // namespace
 
@@ -985,6 +1405,155 @@ int bf_bank_import_filters(bf_bank* b, const uint32_t* ids, uint64_t count, cons
     HIPCHK(b, hipGetLastError());
     HIPCHK(b, hipStreamSynchronize(b->stream));
     return BF_OK;
+}
+
+int bf_bank_fold(bf_bank* b, uint32_t op, const uint32_t* dst_ids, const uint64_t* seg, const uint32_t* src_ids,
+                 uint64_t groups, uint8_t* changed, uint64_t* set_bits) {
+    if (!b) return BF_EINVAL;
+    CallScope cs(b);
+    if (!seg || !src_ids) return bank_err(b, BF_EINVAL, "seg / src_ids is NULL");
+    int rc = check_fold_op(b, op, dst_ids != nullptr);
+    if (rc) return rc;
+    if (seg[0] != 0) return bank_err(b, BF_EINVAL, "seg[0] must be 0, got %llu", (unsigned long long)seg[0]);
+    for (uint64_t g = 0; g < groups; ++g) {
+        if (seg[g + 1] < seg[g])
+            return bank_err(b, BF_EINVAL, "group %llu: seg must be non-decreasing (seg[%llu] = %llu after %llu)",
+                            (unsigned long long)g, (unsigned long long)(g + 1), (unsigned long long)seg[g + 1],
+                            (unsigned long long)seg[g]);
+        if (seg[g + 1] == seg[g])
+            return bank_err(b, BF_EINVAL, "group %llu is empty (the AND of nothing is not a filter)", (unsigned long long)g);
+    }
+    if (groups == 0) return BF_OK;
+    const uint64_t n_src = seg[groups];
+    for (uint64_t i = 0; i < n_src; ++i)
+        if ((uint64_t)src_ids[i] >= b->n_filters)
+            return bank_err(b, BF_EINVAL, "src_ids[%llu] = %u is not below n_filters = %llu", (unsigned long long)i,
+                            src_ids[i], (unsigned long long)b->n_filters);
+    if (dst_ids) {
+        // a destination is written by one group and read by no other: sorted (id, group) pairs
+        std::vector<std::pair<uint32_t, uint64_t>> owner(groups);
+        for (uint64_t g = 0; g < groups; ++g) {
+            if ((uint64_t)dst_ids[g] >= b->n_filters)
+                return bank_err(b, BF_EINVAL, "dst_ids[%llu] = %u is not below n_filters = %llu", (unsigned long long)g,
+                                dst_ids[g], (unsigned long long)b->n_filters);
+            owner[g] = {dst_ids[g], g};
+        }
+        std::sort(owner.begin(), owner.end());
+        uint64_t twice = UINT64_MAX;   // the first group (in list order) whose destination an earlier group has
+        for (uint64_t i = 1; i < groups; ++i)
+            if (owner[i].first == owner[i - 1].first) twice = std::min(twice, owner[i].second);
+        if (twice != UINT64_MAX) {
+            uint64_t other = 0;
+            while (dst_ids[other] != dst_ids[twice]) ++other;
+            return bank_err(b, BF_EINVAL, "dst_ids[%llu] = %u is also the destination of group %llu", (unsigned long long)twice,
+                            dst_ids[twice], (unsigned long long)other);
+        }
+        for (uint64_t g = 0; g < groups; ++g)
+            for (uint64_t i = seg[g]; i < seg[g + 1]; ++i) {
+                auto it = std::lower_bound(owner.begin(), owner.end(), std::make_pair(src_ids[i], (uint64_t)0));
+                if (it != owner.end() && it->first == src_ids[i] && it->second != g)
+                    return bank_err(b, BF_EINVAL, "group %llu reads filter %u (src_ids[%llu]), the destination of group %llu: "
+                                                  "the result would depend on the order of the groups",
+                                    (unsigned long long)g, src_ids[i], (unsigned long long)i, (unsigned long long)it->second);
+            }
+    }
+    // staged as [seg | set_bits | src_ids | dst_ids | changed]: the 8-byte fields first
+    uint64_t total = 0;
+    if (groups > (1ull << 56) || n_src > (1ull << 56)) return bank_err(b, BF_EINVAL, "too many groups or sources");
+    const uint64_t off_sb = (groups + 1) * 8, off_src = off_sb + groups * 8, off_dst = off_src + n_src * 4;
+    const uint64_t off_chg = off_dst + groups * 4;
+    total = off_chg + groups;
+    if (int orc = cs.open(b->stream)) return orc;
+    if ((rc = grow(b, (void**)&b->d_io, &b->io_cap, total))) return rc;
+    uint8_t* io = b->d_io;
+    HIPCHK(b, hipMemcpyAsync(io, seg, (groups + 1) * 8, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(b, hipMemcpyAsync(io + off_src, src_ids, n_src * 4, hipMemcpyHostToDevice, b->stream));
+    if (dst_ids) HIPCHK(b, hipMemcpyAsync(io + off_dst, dst_ids, groups * 4, hipMemcpyHostToDevice, b->stream));
+    if ((rc = launch_fold(b, op, dst_ids ? reinterpret_cast<const uint32_t*>(io + off_dst) : nullptr,
+                          reinterpret_cast<const uint64_t*>(io), reinterpret_cast<const uint32_t*>(io + off_src), groups,
+                          n_src, changed ? io + off_chg : nullptr,
+                          set_bits ? reinterpret_cast<uint64_t*>(io + off_sb) : nullptr, b->stream)))
+        return rc;
+    if (set_bits) HIPCHK(b, hipMemcpyAsync(set_bits, io + off_sb, groups * 8, hipMemcpyDeviceToHost, b->stream));
+    if (changed) HIPCHK(b, hipMemcpyAsync(changed, io + off_chg, groups, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(b, hipStreamSynchronize(b->stream));   // the lists are the caller's again
+    return BF_OK;
+}
+
+int bf_bank_fold_dev(bf_bank* b, uint32_t op, const uint32_t* d_dst_ids, const uint64_t* d_seg, const uint32_t* d_src_ids,
+                     uint64_t groups, uint64_t n_src, uint8_t* d_changed, uint64_t* d_set_bits, void* stream) {
+    if (!b) return BF_EINVAL;
+    CallScope cs(b);
+    int rc = check_fold_op(b, op, d_dst_ids != nullptr);
+    if (rc) return rc;
+    if (groups == 0) return BF_OK;
+    if (!d_seg || !d_src_ids) return bank_err(b, BF_EINVAL, "NULL device pointer (d_seg / d_src_ids)");
+    if ((reinterpret_cast<uintptr_t>(d_seg) & 7u) || (reinterpret_cast<uintptr_t>(d_set_bits) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_src_ids) & 3u) || (reinterpret_cast<uintptr_t>(d_dst_ids) & 3u))
+        return bank_err(b, BF_EINVAL, "misaligned device pointer (d_seg and d_set_bits: 8 bytes, d_src_ids and d_dst_ids: 4)");
+    if (groups > (1ull << 56)) return bank_err(b, BF_EINVAL, "too many groups");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (int orc = cs.open(s)) return orc;
+    return launch_fold(b, op, d_dst_ids, d_seg, d_src_ids, groups, n_src, d_changed, d_set_bits, s);
+}
+
+int bf_bank_overlap(bf_bank* b, const uint32_t* row_ids, uint64_t rows, const uint32_t* col_ids, uint64_t cols,
+                    uint64_t* out) {
+    if (!b) return BF_EINVAL;
+    CallScope cs(b);
+    if (rows == 0 || cols == 0) return BF_OK;
+    uint64_t out_bytes = 0;
+    int rc = check_overlap(b, row_ids, rows, col_ids, cols, &out_bytes);
+    if (rc) return rc;
+    if (!out) return bank_err(b, BF_EINVAL, "out is NULL");
+    for (uint64_t i = 0; row_ids && i < rows; ++i)
+        if ((uint64_t)row_ids[i] >= b->n_filters)
+            return bank_err(b, BF_EINVAL, "row_ids[%llu] = %u is not below n_filters = %llu", (unsigned long long)i,
+                            row_ids[i], (unsigned long long)b->n_filters);
+    for (uint64_t i = 0; col_ids && i < cols; ++i)
+        if ((uint64_t)col_ids[i] >= b->n_filters)
+            return bank_err(b, BF_EINVAL, "col_ids[%llu] = %u is not below n_filters = %llu", (unsigned long long)i,
+                            col_ids[i], (unsigned long long)b->n_filters);
+    if (int orc = cs.open(b->stream)) return orc;
+    // both lists side by side in d_list; without col_ids the columns are the row list
+    const uint64_t n_row = row_ids ? rows : 0, n_col = col_ids ? cols : 0;
+    const uint32_t *d_rows = nullptr, *d_cols = nullptr;
+    if (n_row + n_col) {
+        if ((rc = grow(b, (void**)&b->d_list, &b->list_cap, (n_row + n_col) * 4))) return rc;
+        if (n_row) HIPCHK(b, hipMemcpyAsync(b->d_list, row_ids, n_row * 4, hipMemcpyHostToDevice, b->stream));
+        if (n_col) HIPCHK(b, hipMemcpyAsync(b->d_list + n_row, col_ids, n_col * 4, hipMemcpyHostToDevice, b->stream));
+        d_rows = n_row ? b->d_list : nullptr;
+        d_cols = n_col ? b->d_list + n_row : d_rows;
+    }
+    // runs of rows whose counts stay under kOverlapOutCap; one run is the whole (then maybe symmetric) matrix
+    const uint64_t max_rows = std::max<uint64_t>(1, kOverlapOutCap / (cols * 8));
+    for (uint64_t a = 0; a < rows; a += max_rows) {
+        const uint64_t cn = std::min<uint64_t>(max_rows, rows - a);
+        if ((rc = grow(b, (void**)&b->d_io, &b->io_cap, cn * cols * 8))) return rc;
+        if ((rc = launch_overlap(b, d_rows ? d_rows + a : nullptr, a, cn, d_cols, cols, !col_ids && cn == rows,
+                                 reinterpret_cast<uint64_t*>(b->d_io), b->stream)))
+            return rc;
+        HIPCHK(b, hipMemcpyAsync(out + a * cols, b->d_io, cn * cols * 8, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(b, hipStreamSynchronize(b->stream));   // d_io is free again
+    }
+    return BF_OK;
+}
+
+int bf_bank_overlap_dev(bf_bank* b, const uint32_t* d_row_ids, uint64_t rows, const uint32_t* d_col_ids, uint64_t cols,
+                        uint64_t* d_out, void* stream) {
+    if (!b) return BF_EINVAL;
+    CallScope cs(b);
+    if (rows == 0 || cols == 0) return BF_OK;
+    uint64_t out_bytes = 0;
+    int rc = check_overlap(b, d_row_ids, rows, d_col_ids, cols, &out_bytes);
+    if (rc) return rc;
+    if (!d_out) return bank_err(b, BF_EINVAL, "NULL device pointer (d_out)");
+    if ((reinterpret_cast<uintptr_t>(d_out) & 7u) || (reinterpret_cast<uintptr_t>(d_row_ids) & 3u) ||
+        (reinterpret_cast<uintptr_t>(d_col_ids) & 3u))
+        return bank_err(b, BF_EINVAL, "misaligned device pointer (d_out: 8 bytes, d_row_ids and d_col_ids: 4)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (int orc = cs.open(s)) return orc;
+    return launch_overlap(b, d_row_ids, 0, rows, d_col_ids ? d_col_ids : d_row_ids, cols, !d_col_ids, d_out, s);
 }
 
 }  // extern "C"

@@ -26,6 +26,17 @@ events around each, median / min / max of --runs runs after --warmup; the answer
 once outside the timed region.
 
     python tools/bench_bank.py --across [--hashes 7] [--runs 25] [--out profiles/bank_across.json]
+
+--combine times the bank's folds and overlap matrix (bf_bank_fold_dev, bf_bank_overlap_dev) against
+what there was before them: ``export_filters`` of the sources, a numpy OR and ``import_redis`` of
+the destination for a roll-up; ``export_filters`` of the list and host counts of the ANDs for the
+matrix.  Both baselines include their copies.  The same method: the two alternate, HIP events
+around each, median / min / max, the results compared once outside the timed region.  Before
+each timed roll-up its destinations are cleared (untimed), so every vector is stored.  The 10k @
+1 % filters hold 5,000 random keys each; the 120-MB ones (m = 958,505,838) are random strings,
+every bit set with probability 1/2.
+
+    python tools/bench_bank.py --combine [--only small|many|big] [--runs 25] [--out profiles/bank_combine.json]
 """
 import argparse
 import json
@@ -248,6 +259,173 @@ def run_across(pkg, m, k, label, n, listed, nf, runs, warmup) -> dict:
     return res
 
 
+# ---- --combine: folds and the overlap matrix against export + numpy + import ----------------------
+
+BIG_M = 958_505_838     # 100M @ 1 %: 120 MB a filter
+
+
+def i64(a):
+    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()
+
+
+def i32(a):
+    return torch.from_numpy(np.ascontiguousarray(a, np.uint32).view(np.int32).copy()).cuda()
+
+
+def timed_alternating(fns, befores, runs: int, warmup: int):
+    """timed_pair with an untimed step before each call (None: nothing)."""
+    ms = [[] for _ in fns]
+    for i in range(warmup + runs):
+        for which, fn in enumerate(fns):
+            if befores[which]:
+                befores[which]()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if i >= warmup:
+                ms[which].append(e0.elapsed_time(e1))
+    return [sorted(x) for x in ms]
+
+
+def span(ms) -> dict:
+    return {"ms": round(statistics.median(ms), 4), "min_ms": round(ms[0], 4), "max_ms": round(ms[-1], 4)}
+
+
+def ratios(res: dict, new, base) -> dict:
+    res["new"], res["baseline"] = span(new), span(base)
+    res["ratio"] = round(res["baseline"]["ms"] / res["new"]["ms"], 1)
+    res["ratio_min"] = round(base[0] / new[-1], 1)      # the baseline's fastest run over the new call's slowest
+    res["ratio_max"] = round(base[-1] / new[0], 1)
+    res["ranges_overlap"] = bool(base[0] <= new[-1])
+    print("%s: %.4f ms against %.4f ms" % (res["shape"], res["new"]["ms"], res["baseline"]["ms"]), file=sys.stderr,
+          flush=True)
+    return res
+
+
+def fill_random_bits(bank) -> None:
+    """Every filter a random string (each bit set with probability 1/2), imported."""
+    rng = np.random.default_rng(0xB16)
+    nbytes = (bank.m + 7) // 8
+    for f in range(bank.n_filters):
+        s = rng.integers(0, 256, nbytes, dtype=np.uint8)
+        if bank.m % 8:
+            s[-1] &= (0xFF << (8 - bank.m % 8)) & 0xFF
+        bank.import_redis(np.array([f], np.uint32), [s.tobytes()])
+
+
+def host_overlap(buf) -> np.ndarray:
+    """AND counts of every pair of exported filters on the host: an exact float matmul of the
+    unpacked bits while a count fits a float32's 24 bits, else popcounts of the ANDed words."""
+    if buf.shape[1] * 8 < 1 << 24:
+        a = np.unpackbits(buf, axis=1).astype(np.float32)
+        return (a @ a.T).astype(np.uint64)
+    w = buf.view(np.uint64)
+    return np.array([[int(np.bitwise_count(x & y).sum(dtype=np.uint64)) for y in w] for x in w], np.uint64)
+
+
+def run_fold(bank, label, sources, dst, runs, warmup) -> dict:
+    """Roll-ups dst[g] = OR(sources[g]): bf_bank_fold_dev against export, numpy OR, import."""
+    groups = len(sources)
+    seg = np.zeros(groups + 1, np.uint64)
+    np.cumsum([len(s) for s in sources], out=seg[1:])
+    src = np.concatenate(sources).astype(np.uint32)
+    dst = np.asarray(dst, np.uint32)
+    d_seg, d_src, d_dst = i64(seg), i32(src), i32(dst)
+    d_ch = torch.zeros(groups, dtype=torch.uint8, device="cuda")
+    d_sb = torch.zeros(groups, dtype=torch.int64, device="cuda")
+    state = {}
+
+    def new():
+        bank.fold_dev("or", d_seg.data_ptr(), d_src.data_ptr(), groups, len(src), d_dst.data_ptr(), d_ch.data_ptr(),
+                      d_sb.data_ptr(), stream=0)
+
+    def baseline():
+        buf, _ = bank.export_filters(src)
+        out = np.bitwise_or.reduceat(buf, seg[:-1].astype(np.int64), axis=0)
+        nbytes = (bank.m + 7) // 8
+        bank.import_redis(dst, [row[:nbytes].tobytes() for row in out])
+        state["want"] = out
+
+    t_new, t_base = timed_alternating([new, baseline], [lambda: bank.clear_dev(d_dst.data_ptr(), groups, stream=0), None],
+                                      runs, warmup)
+    bank.clear_dev(d_dst.data_ptr(), groups, stream=0)
+    new()
+    torch.cuda.synchronize()
+    bank.sync()
+    got, _ = bank.export_filters(dst)
+    assert np.array_equal(got, state["want"]), "the fold and the host OR differ"
+    assert bool(d_ch.all()) and int(d_sb.sum()) == int(bank.bitcount(dst).sum())
+    res = ratios({"shape": label, "groups": groups, "sources": len(src), "stride": bank.stride}, t_new, t_base)
+    moved = (len(src) + 2 * groups) * bank.stride        # every source and the old destination read, the new one written
+    res["new_GB_per_s"] = round(moved / (res["new"]["ms"] * 1e-3) / 1e9, 1)
+    return res
+
+
+def run_overlap(bank, label, ids, runs, warmup, with_fold=False) -> dict:
+    """The matrix of a list against itself: bf_bank_overlap_dev against export + host counts."""
+    n = bank.n_filters if ids is None else len(ids)
+    listed = np.arange(n, dtype=np.uint32) if ids is None else np.asarray(ids, np.uint32)
+    d_ids = None if ids is None else i32(listed)
+    d_out = torch.full((n * n,), -1, dtype=torch.int64, device="cuda")
+    state = {}
+
+    def new():
+        bank.overlap_dev(d_out.data_ptr(), 0 if d_ids is None else d_ids.data_ptr(), n, stream=0)
+
+    def baseline():
+        state["want"] = host_overlap(bank.export_filters(ids)[0])
+
+    t_new, t_base = timed_alternating([new, baseline], [None, None], runs, warmup)
+    torch.cuda.synchronize()
+    bank.sync()
+    got = d_out.cpu().numpy().view(np.uint64).reshape(n, n)
+    assert np.array_equal(got, state["want"]), "the overlap kernel and the host counts differ"
+    res = ratios({"shape": label, "rows": n, "cols": n, "stride": bank.stride}, t_new, t_base)
+    res["new_filter_GB_per_s"] = round(len(set(listed.tolist())) * bank.stride / (res["new"]["ms"] * 1e-3) / 1e9, 1)
+    if with_fold:   # informational: the same matrix as n * n count-only AND pairs of the streaming fold
+        pairs = np.stack([np.repeat(listed, n), np.tile(listed, n)], axis=1).reshape(-1)
+        d_seg, d_src = i64(np.arange(n * n + 1, dtype=np.uint64) * 2), i32(pairs)
+        d_sb = torch.zeros(n * n, dtype=torch.int64, device="cuda")
+        (t_fold,) = timed_alternating(
+            [lambda: bank.fold_dev("and", d_seg.data_ptr(), d_src.data_ptr(), n * n, 2 * n * n, d_set_bits=d_sb.data_ptr(),
+                                   stream=0)], [None], runs, warmup)
+        torch.cuda.synchronize()
+        bank.sync()
+        assert np.array_equal(d_sb.cpu().numpy().view(np.uint64).reshape(n, n), got)
+        res["fold_pairs"] = span(t_fold)
+        res["fold_pairs_over_overlap"] = round(res["fold_pairs"]["ms"] / res["new"]["ms"], 1)
+    return res
+
+
+def run_combine(pkg, m, k, runs, warmup, only=None) -> list:
+    rng = np.random.default_rng(0xC0B1)
+    shapes = []
+    if only in (None, "small"):
+        with pkg.FilterBank(m, k, 1000, device=0) as bank:
+            fill_half(bank, 1000)
+            bank.clear(np.array([999], np.uint32))
+            shapes.append(run_fold(bank, "1 roll-up of 30 of 10^3 filters", [rng.choice(999, 30, replace=False)], [999],
+                                   runs, warmup))
+            fill_half(bank, 1000)
+            shapes.append(run_overlap(bank, "overlap of all 10^3 filters", None, runs, warmup, with_fold=True))
+            shapes.append(run_overlap(bank, "overlap of 32 x 32 of 10^3 filters", rng.choice(1000, 32, replace=False), runs,
+                                      warmup))
+    if only in (None, "many"):
+        with pkg.FilterBank(m, k, 10_000, device=0) as bank:
+            fill_half(bank, 10_000)
+            sources = [rng.choice(9000, 7, replace=False) for _ in range(1000)]
+            shapes.append(run_fold(bank, "10^3 roll-ups of 7 of 10^4 filters", sources, np.arange(9000, 10_000), runs, warmup))
+    if only in (None, "big"):
+        with pkg.FilterBank(BIG_M, 7, 5, device=0) as bank:
+            fill_random_bits(bank)
+            shapes.append(run_fold(bank, "1 fold of 4 filters of 120 MB", [np.arange(4)], [4], runs, warmup))
+            shapes.append(run_overlap(bank, "overlap of 2 x 2 filters of 120 MB", [1, 2], runs, warmup))
+    return shapes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--filters", default="1000,100000")
@@ -258,6 +436,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--across", action="store_true",
                     help="time the cross query against the crossed batch instead (profiles/bank_across.json)")
+    ap.add_argument("--combine", action="store_true",
+                    help="time folds and the overlap matrix against export + numpy + import (profiles/bank_combine.json)")
+    ap.add_argument("--only", choices=["small", "many", "big"], default=None,
+                    help="--combine: the shapes of one bank only (10^3 filters, 10^4 filters, 5 x 120 MB)")
     args = ap.parse_args()
     if args.runs < 20:
         ap.error("--runs must be at least 20 (the medians quoted in DESIGN.md)")
@@ -271,6 +453,16 @@ def main():
         doc = {"tool": "tools/bench_bank.py --across", "device": torch.cuda.get_device_name(0), "m": m, "k": k,
                "key_bytes": KEY_BYTES, "fill_per_filter": FILL_PER_FILTER, "runs": args.runs, "warmup": args.warmup,
                "shapes": [run_across(pkg, m, k, *shape, args.runs, args.warmup) for shape in ACROSS_SHAPES]}
+        line = json.dumps(doc)
+        print(line)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return
+    if args.combine:
+        doc = {"tool": "tools/bench_bank.py --combine", "device": torch.cuda.get_device_name(0), "m": m, "k": k,
+               "big_m": BIG_M, "fill_per_filter": FILL_PER_FILTER, "runs": args.runs, "warmup": args.warmup,
+               "shapes": run_combine(pkg, m, k, args.runs, args.warmup, args.only)}
         line = json.dumps(doc)
         print(line)
         if args.out:
