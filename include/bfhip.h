@@ -646,7 +646,38 @@ int  bf_lua_index(double entries, uint64_t count, uint32_t* layer);
  *                        over a filter's keys is exactly "this filter's string changed": the
  *                        reference's !found (ruby.rb:61-62), which drives EXPIRE per key_name.
  *                        Per key it is NOT the sequential flag (which key of several wins a bit is
- *                        unspecified; bf_insert_many's per_key_new has no counterpart here).
+ *                        unspecified); that is bf_bank_insert_many_seq's per_key_new.
+ *   bf_bank_insert_many_seq  the same insert with the exact sequential flag: first-seen dedup,   ruby.rb:57-63
+ *                        the reference's check-then-add loop (benchmark/bf_10_000.rb:34-43:
+ *                        include? then insert) run per key_name over a whole mixed batch.
+ *                        per_key_new[j] (nullable, n bytes) = 1 iff, inserting the pairs
+ *                        (filter_ids[j], key j) one at a time in batch order, key j flipped at least
+ *                        one bit of its filter 0 -> 1: ruby.rb:61's !found for that key, the
+ *                        counterpart of bf_insert_many's per_key_new.  So !per_key_new[j] is
+ *                        include?-before-insert; the same key sent to two filters is new in both;
+ *                        the same (filter, key) pair twice in a batch is new at its first place
+ *                        only; the OR of the flags over a filter's keys is "this filter's string
+ *                        changed".  The bank's bits afterwards are exactly those
+ *                        bf_bank_insert_many leaves.  A call runs in chunks of at most
+ *                        bf_bank_seq_plan's chunk_keys keys (the _dev form cuts the batch itself,
+ *                        the host form cuts by cfg's batch_keys / batch_bytes as well), each chunk
+ *                        after the one before on the stream, which gives the one-by-one result.
+ *                        Its scratch (a first-index table, 16 B of digest and 8 B of mask per key)
+ *                        belongs to the bank and grows on demand: the _dev form synchronises (the
+ *                        wait of bf_bank_sync, without its report) ONLY when the scratch has to
+ *                        grow, so a repeated shape never does.  Refusals are bf_bank_insert_many's
+ *                        (_dev: bf_bank_insert_many_dev's; a skipped key reports 0).
+ *   bf_bank_set_seq_form forces the table's form for the bank's later calls where it is legal
+ *                        (BF_BANK_SEQ_HASH: always; BF_BANK_SEQ_DIRECT: up to 2^28 bits of bank;
+ *                        BF_BANK_SEQ_AUTO, the default: the bank's own rule).  It never changes a
+ *                        result.  The library reads no environment variable for it: the Python
+ *                        binding's FilterBank applies BFHIP_BANK_SEQ_FORM=hash|direct through
+ *                        this call when it creates a bank.  An unknown form is BF_EINVAL.
+ *   bf_bank_seq_plan     how bf_bank_insert_many_seq* runs a batch of n keys (host only, no launch;
+ *                        each output nullable): direct = 1 when the first-index table is one uint32
+ *                        per bit of the bank (one atomicMin per 0-probe), 0 when it is a hash table
+ *                        of (bit number, index) with at least 2 n k slots; chunk_keys = min(n, the
+ *                        chunk bound of k); scratch_bytes = what the bank allocates for it.
  *   bf_bank_include_many Ruby#include? of key j in filter filter_ids[j]: out[j] = 0 / 1   ruby.rb:20-30
  *   bf_bank_include_across  Ruby#include? of key j in EVERY listed filter: which of the bank's   ruby.rb:20-30
  *                        filters have seen this key.  A key's k offsets (ruby.rb:41-55) depend on
@@ -748,6 +779,18 @@ int  bf_bank_insert_many(bf_bank* b, const uint8_t* key_bytes, const uint64_t* o
 int  bf_bank_insert_many_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets,
                              const uint32_t* d_filter_ids, uint64_t n, uint8_t* d_key_flipped /* nullable */,
                              void* stream);
+int  bf_bank_insert_many_seq(bf_bank* b, const uint8_t* key_bytes, const uint64_t* offsets, const uint32_t* filter_ids,
+                             uint64_t n, uint8_t* per_key_new /* nullable, n bytes */);
+int  bf_bank_insert_many_seq_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets,
+                                 const uint32_t* d_filter_ids, uint64_t n, uint8_t* d_per_key_new /* nullable */,
+                                 void* stream);
+#define BF_BANK_SEQ_AUTO   0u
+#define BF_BANK_SEQ_HASH   1u
+#define BF_BANK_SEQ_DIRECT 2u
+int  bf_bank_set_seq_form(bf_bank* b, uint32_t form /* BF_BANK_SEQ_* */);
+/* no launch: how a batch of n keys will run */
+int  bf_bank_seq_plan(const bf_bank* b, uint64_t n, uint32_t* direct /* 1: one word per bank bit */,
+                      uint64_t* chunk_keys, uint64_t* scratch_bytes);
 int  bf_bank_include_many(bf_bank* b, const uint8_t* key_bytes, const uint64_t* offsets, const uint32_t* filter_ids,
                           uint64_t n, uint8_t* out /* n bytes, 0/1 */);
 int  bf_bank_include_many_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets,

@@ -167,6 +167,10 @@ SIGNATURES = {
     "bf_bank_sync": (ctypes.c_int, [_vp]),
     "bf_bank_insert_many": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "bf_bank_insert_many_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "bf_bank_insert_many_seq": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
+    "bf_bank_insert_many_seq_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "bf_bank_set_seq_form": (ctypes.c_int, [_vp, _u32]),
+    "bf_bank_seq_plan": (ctypes.c_int, [_vp, _u64, _u32p, _u64p, _u64p]),
     "bf_bank_include_many": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "bf_bank_include_many_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
     "bf_bank_across_row_bytes": (ctypes.c_int, [_u64, _u64p]),
@@ -886,6 +890,20 @@ class FilterBank(_Handle):
                                            ctypes.byref(db)), h)
         self.m, self.k, self.n_filters, self.stride, self.device_bytes = m.value, kk.value, nf.value, st.value, db.value
         self.device = int(device)
+        # BFHIP_BANK_SEQ_FORM=hash|direct, read once here: the form of insert_many_seq's table
+        # where it is legal.  It never changes a result (the tests run both forms with it).
+        form = os.environ.get("BFHIP_BANK_SEQ_FORM")
+        if form in self.SEQ_FORMS:
+            self.set_seq_form(form)
+
+    SEQ_FORMS = {"auto": 0, "hash": 1, "direct": 2}   # BF_BANK_SEQ_*
+
+    def set_seq_form(self, form: str) -> None:
+        """Force the first-index table of ``insert_many_seq*`` (``seq_plan``) to ``'hash'`` or
+        ``'direct'`` where that form is legal, or back to the bank's own choice (``'auto'``)."""
+        if form not in self.SEQ_FORMS:
+            raise ArgumentError("form must be one of %s, got %r" % (sorted(self.SEQ_FORMS), form))
+        _bank_check(self._lib.bf_bank_set_seq_form(self.handle, self.SEQ_FORMS[form]), self._h)
 
     def sync(self) -> None:
         """Wait for the bank's work; ArgumentError (once) when a ``*_dev`` call's kernel skipped
@@ -914,6 +932,26 @@ class FilterBank(_Handle):
         _bank_check(self._lib.bf_bank_insert_many(self.handle, _ptr(keys), _ptr(offsets), _ptr(ids), n, _ptr(kf)),
                     self._h)
         return kf[:n] if key_flipped else None
+
+    def insert_many_seq(self, keys: np.ndarray, offsets: np.ndarray, filter_ids: np.ndarray) -> np.ndarray:
+        """``insert_many`` with the exact sequential flag (first-seen dedup): [j] is 1 iff,
+        inserting the pairs (filter_ids[j], key j) one at a time in batch order, key j flipped a
+        bit of its filter (ruby.rb:57-63); its complement is include?-before-insert.  The bits
+        left behind are ``insert_many``'s."""
+        keys, offsets, ids, n = self._batch(keys, offsets, filter_ids)
+        new = np.zeros(max(n, 1), np.uint8)
+        _bank_check(self._lib.bf_bank_insert_many_seq(self.handle, _ptr(keys), _ptr(offsets), _ptr(ids), n, _ptr(new)),
+                    self._h)
+        return new[:n]
+
+    def seq_plan(self, n: int) -> Tuple[bool, int, int]:
+        """How ``insert_many_seq*`` runs a batch of ``n`` keys, without a launch: (direct: the
+        first-index table is one word per bit of the bank, not a hash table; keys per chunk; bytes
+        of scratch)."""
+        direct, chunk, scratch = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint64()
+        _bank_check(self._lib.bf_bank_seq_plan(self.handle, int(n), ctypes.byref(direct), ctypes.byref(chunk),
+                                               ctypes.byref(scratch)), self._h)
+        return bool(direct.value), chunk.value, scratch.value
 
     def include_many(self, keys: np.ndarray, offsets: np.ndarray, filter_ids: np.ndarray) -> np.ndarray:
         keys, offsets, ids, n = self._batch(keys, offsets, filter_ids)
@@ -1054,6 +1092,13 @@ class FilterBank(_Handle):
                         stream=None) -> None:
         _bank_check(self._lib.bf_bank_insert_many_dev(self.handle, d_keys, d_offsets, d_filter_ids, int(n),
                                                       d_key_flipped or None, self._s(stream)), self._h)
+
+    def insert_many_seq_dev(self, d_keys: int, d_offsets: int, d_filter_ids: int, n: int, d_per_key_new: int = 0,
+                            stream=None) -> None:
+        """``insert_many_seq`` on device arrays.  Synchronises only when the bank's scratch has to
+        grow (the first call of a shape; see ``seq_plan``)."""
+        _bank_check(self._lib.bf_bank_insert_many_seq_dev(self.handle, d_keys, d_offsets, d_filter_ids, int(n),
+                                                          d_per_key_new or None, self._s(stream)), self._h)
 
     def include_many_dev(self, d_keys: int, d_offsets: int, d_filter_ids: int, n: int, d_out: int,
                          stream=None) -> None:

@@ -5,7 +5,9 @@ In the reference ``key_name`` names a filter (lib/redis/bloomfilter.rb:14, ruby.
 and an application keeps one per tenant, per day or per feed.  A bank fixes the list of key
 names at construction (``key_names[i]`` is filter ``i``), sizes every filter with
 ``Bloomfilter.optimal_m`` / ``optimal_k`` (bloomfilter.rb:25-28) and takes a mixed batch of
-``(key name, key)`` pairs in one launch.  ``which`` / ``include_across`` ask the question only a
+``(key name, key)`` pairs in one launch.  ``first_seen_many`` is first-seen dedup over such a
+batch: insert, and say per pair whether it was new, exactly as if the pairs had gone in one by
+one (bf_bank_insert_many_seq).  ``which`` / ``include_across`` ask the question only a
 bank can answer in one launch: which of the key names have seen this key.  ``merge`` / ``rollup``
 / ``union_size`` / ``intersection_size`` / ``overlap`` combine key names with each other on the
 device (bf_bank_fold, bf_bank_overlap).
@@ -43,6 +45,9 @@ class BankFilter:
 
     def insert(self, data, expire=None):
         return self.bank.insert(self.key_name, data, expire)
+
+    def first_seen(self, key, expire=None) -> bool:
+        return self.bank.first_seen(self.key_name, key, expire)
 
     def include(self, key) -> bool:
         return self.bank.include(self.key_name, key)
@@ -139,7 +144,13 @@ class BloomfilterBank:
         self._expired()
         ids, buf, offs = self._batch(names, keys)
         flipped = self.bank.insert_many(buf, offs, ids)
-        changed = sorted(set(ids[flipped != 0].tolist()))
+        return self._inserted(ids, flipped, expire)
+
+    def _inserted(self, ids: np.ndarray, new: np.ndarray, expire) -> Set[str]:
+        """The Redis side of an insert, per key name whose string changed (``ids[new != 0]``):
+        write-through SETRANGE or dirty marking, EXPIRE and deadline arming (ruby.rb:61-62).
+        Returns those key names."""
+        changed = sorted(set(ids[new != 0].tolist()))
         expire = self._expire(expire)
         armed = expire is not None and expire is not False   # ruby.rb:62: 0 counts
         write = self.redis is not None and self.sync_mode == "write_through"
@@ -157,6 +168,21 @@ class BloomfilterBank:
 
     def insert(self, name, key, expire=None) -> bool:
         return bool(self.insert_many([name], [key], expire))
+
+    # -- first-seen dedup: benchmark/bf_10_000.rb:34-43's include? then insert, per key name
+    def first_seen_many(self, names: Iterable, keys: Iterable, expire=None) -> np.ndarray:
+        """Insert the batch and answer, per pair, "had I seen this before?" negated: [j] is True iff
+        ``(names[j], keys[j])`` was not in its filter before its own insert, the pairs taken one
+        at a time in batch order (so a pair repeated in the batch is True at its first place only).
+        Towards Redis it behaves like ``insert_many``."""
+        self._expired()
+        ids, buf, offs = self._batch(names, keys)
+        new = self.bank.insert_many_seq(buf, offs, ids)
+        self._inserted(ids, new, expire)
+        return new.astype(bool)
+
+    def first_seen(self, name, key, expire=None) -> bool:
+        return bool(self.first_seen_many([name], [key], expire)[0])
 
     # -- ruby.rb:20-30
     def include_many(self, names: Iterable, keys: Iterable) -> np.ndarray:

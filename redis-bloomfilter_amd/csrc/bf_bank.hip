@@ -14,6 +14,8 @@
 //   bank_keys_kernel    insert / include?: one lane per key, 256 keys per workgroup staged
 //                       through LDS (bfdev::for_key_tile), SHA-1 and the offsets of ruby.rb:41-55
 //                       from bf_device.h, the k probes inside the lane's own filter.
+//   bank_seq_*_kernel   insert with the exact sequential per-key flag (first-seen dedup): bf_seq.hip's
+//                       candidates / mark pair, the first-index table keyed by the bank-wide bit.
 //   bank_across_kernel  include? of one key in many filters: the same tile, hashed once per
 //                       workgroup, its k bit positions tested in every filter of a chunk of the
 //                       list; one 64-entry mask word per lane and group.
@@ -135,6 +137,139 @@ __global__ __launch_bounds__(kBankTile) void bank_keys_kernel(BfGeom g, uint64_t
                 if (out8) out8[j] = (uint8_t)flipped;
             }
         });
+}
+
+// ---- sequential per-key flags: the mixed batch inserted one pair at a time ---------------------
+
+// bf_seq.hip's two-kernel scheme with the bit space widened to the whole bank.  Inserting the
+// pairs (ids[j], key j) one by one in batch order (ruby.rb:57-63 per key_name), key j is new iff
+// one of its bits was 0 before the batch and no earlier key of the batch going to the SAME filter
+// probes it.  With first(f, b) = the smallest batch index whose key goes to filter f and probes
+// bit b:
+//
+//     new(j)  <=>  exists probe b of j:  prebit(ids[j], b) == 0  and  first(ids[j], b) == j
+//
+// A bit is named bank-wide: id * stride * 8 + o, which is also its position in the allocation.
+//   1. bank_seq_candidates: hash, test every probe against the pre-batch bits (plain loads, the
+//      bank is not written) and record the min index j under the bit's number for each 0 bit —
+//      DIRECT: one uint32 per bit of the bank, one atomicMin; else an open-addressing table keyed
+//      by bit number + 1 (64-bit atomicCAS claim, then atomicMin), at most half full.  The digest
+//      and the key's mask of 0-probes go to scratch.
+//   2. bank_seq_mark: new(j) from the table, then the 0-probes ORed in.
+// Indices are 32-bit and relative to the chunk (bf_seq_chunk_keys); chunks run in stream order.
+
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {   // SplitMix64 finalizer, as in bf_seq.hip
+    x ^= x >> 30;
+    x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27;
+    x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+
+// cand[j] = the mask of key j's probes whose bit is 0 (probe i: bit i; k <= BF_MAX_K = 64),
+// digests[j] = H0..H3.  A refused key (bank_keys_kernel's rule) has mask 0.  status as there.
+template <bool DIRECT>
+__global__ __launch_bounds__(kBankTile) void bank_seq_candidates_kernel(
+    BfGeom g, uint64_t n_filters, uint64_t stride_words, const uint8_t* __restrict__ keys16,
+    const uint64_t* __restrict__ offsets, uint64_t bias, const uint32_t* __restrict__ ids, uint64_t n,
+    unsigned long long* __restrict__ tkeys, uint32_t* __restrict__ tvals, uint64_t tmask, uint4* __restrict__ digests,
+    unsigned long long* __restrict__ cand, uint32_t* __restrict__ status) {
+    __shared__ uint64_t s_off[kBankTile + 1];
+    __shared__ uint4 s_stage[kBankStageVec + kStageSlackVec];
+    const uint64_t tile0 = (uint64_t)blockIdx.x * kBankTile;
+    const uint32_t cnt = (uint32_t)((n - tile0) < (uint64_t)kBankTile ? (n - tile0) : kBankTile);
+    for_key_tile<kBankTile, kBankStageVec>(keys16, offsets, bias, tile0, cnt, s_off, s_stage, status,
+        [&](auto staged, uint32_t lane, const uint32_t* src, uint32_t s, uint32_t L) {
+            const uint32_t j = (uint32_t)(tile0 + lane);   // chunk-relative: n <= 2^22
+            const uint32_t id = ids[j];
+            // a refused key arrives as the empty key (bank_keys_kernel): every lane hashes, a
+            // skipped one keeps mask 0
+            bool ok = key_ok(s_off[0], s_off[lane], s_off[lane + 1], s_off[cnt], nullptr);
+            if ((uint64_t)id >= n_filters) {
+                status[1] = 1u;
+                ok = false;
+            }
+            uint32_t H[5];
+            sha1_any<decltype(staged)::value>(src, s, L, H);
+            digests[j] = make_uint4(H[0], H[1], H[2], H[3]);
+            unsigned long long cm = 0;
+            if (ok) {
+                const uint32_t* __restrict__ fb = g.bits + (uint64_t)id * stride_words;   // 64-bit word index
+                const uint64_t bit0 = (uint64_t)id * stride_words * 32u;                  // the filter's first bit number
+                const uint32_t k = g.k;
+                for (uint32_t i0 = 0; i0 < k; i0 += kChunk) {
+                    // every load of a round is issued before any is used
+                    uint64_t o[kChunk];
+                    uint32_t v[kChunk];
+#pragma unroll
+                    for (int c = 0; c < kChunk; ++c) {
+                        o[c] = 0; v[c] = 0xFFFFFFFFu;
+                        if (i0 + c < k) {
+                            o[c] = probe_offset(g, H[0], H[1], H[2], H[3], i0 + c);
+                            v[c] = fb[o[c] >> 5];
+                        }
+                    }
+#pragma unroll
+                    for (int c = 0; c < kChunk; ++c) {
+                        if ((v[c] >> ((uint32_t)(o[c] ^ 7u) & 31u)) & 1u) continue;   // set already, or past k
+                        cm |= 1ull << (i0 + c);
+                        const uint64_t bn = bit0 + o[c];
+                        if constexpr (DIRECT) {   // one word per bit of the bank: no claim, no probing
+                            atomicMin(tvals + bn, j);
+                        } else {
+                            const unsigned long long key = bn + 1;   // 0 marks an empty slot
+                            uint64_t slot = mix64(bn) & tmask;
+                            for (;;) {   // the table holds <= half its slots: a free or matching slot exists
+                                const unsigned long long cur = atomicCAS(tkeys + slot, 0ull, key);
+                                if (cur == 0ull || cur == key) {
+                                    atomicMin(tvals + slot, j);
+                                    break;
+                                }
+                                slot = (slot + 1) & tmask;
+                            }
+                        }
+                    }
+                }
+            }
+            cand[j] = cm;
+        });
+}
+
+// out8[j] (nullable) = new(j); every 0-probe of key j is ORed into its filter.
+template <bool DIRECT>
+__global__ __launch_bounds__(kBankTile) void bank_seq_mark_kernel(
+    BfGeom g, uint64_t stride_words, const uint32_t* __restrict__ ids, uint64_t n,
+    const unsigned long long* __restrict__ tkeys, const uint32_t* __restrict__ tvals, uint64_t tmask,
+    const uint4* __restrict__ digests, const unsigned long long* __restrict__ cand, uint8_t* __restrict__ out8) {
+    const uint64_t j = (uint64_t)blockIdx.x * kBankTile + threadIdx.x;
+    if (j >= n) return;
+    uint32_t isnew = 0;
+    unsigned long long cm = cand[j];
+    if (cm) {   // a key with a 0-probe passed the candidates' checks: its id is in range
+        const uint4 H = digests[j];
+        const uint64_t id = ids[j];
+        uint32_t* __restrict__ fb = g.bits + id * stride_words;
+        const uint64_t bit0 = id * stride_words * 32u;
+        while (cm) {
+            const uint32_t i = (uint32_t)__builtin_ctzll(cm);
+            cm &= cm - 1;
+            const uint64_t o = probe_offset(g, H.x, H.y, H.z, H.w, i);
+            const uint64_t bn = bit0 + o;
+            uint64_t slot = bn;
+            if constexpr (!DIRECT) {
+                const unsigned long long key = bn + 1;
+                slot = mix64(bn) & tmask;
+                // claimed by bank_seq_candidates; an empty slot cannot come first, it only ends the walk
+                for (unsigned long long cur = tkeys[slot]; cur != key && cur != 0ull; cur = tkeys[slot])
+                    slot = (slot + 1) & tmask;
+            }
+            isnew |= tvals[slot] == (uint32_t)j ? 1u : 0u;
+            __hip_atomic_fetch_or(fb + (o >> 5), 1u << ((uint32_t)(o ^ 7u) & 31u), __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if (out8) out8[j] = (uint8_t)isnew;
 }
 
 // ---- cross query: one key against many filters ----------------------------------------------
@@ -770,6 +905,10 @@ struct bf_bank : BfHostCore {   // mutex, device, stream, error, stream order: b
     uint64_t io_cap = 0;
     uint32_t* d_list = nullptr;        // a host call's id list
     uint64_t list_cap = 0;
+    // bf_bank_insert_many_seq*: [first-index table | 16 B digest per key | 8 B 0-probe mask per key]
+    uint8_t* d_seq = nullptr;
+    uint64_t seq_cap = 0;
+    uint32_t seq_form = 0;             // bf_bank_set_seq_form: BF_BANK_SEQ_*
 };
 
 namespace {
@@ -896,6 +1035,105 @@ int run_dev(bf_bank* b, int op, const uint8_t* d_keys, const uint64_t* d_off, co
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (int orc = cs.open(s)) return orc;
     return launch_keys(b, op, d_keys, d_off, d_ids, n, d_out, s);
+}
+
+// ---- sequential flags: the plan, the scratch and the chunk loop ------------------------------
+
+constexpr uint64_t kSeqDirectMaxBytes = 1ull << 25;   // a bank of 2^28 bits: a direct table of 1 GiB
+
+uint64_t align256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
+
+// The hash table's slots for n keys of k probes (at most half full): bf_seq.hip's seq_slots.
+uint64_t seq_slots(uint64_t n, uint32_t k) {
+    uint64_t s = 1024;
+    while (s < 2 * n * (uint64_t)k) s <<= 1;
+    return s;
+}
+
+// bf_seq.hip's seq_direct with the bank's bits in place of m: one uint32 per bit of the bank when
+// that table is no larger than the hash table (12 B per slot) it replaces and at most 1 GiB.
+// bf_bank_set_seq_form forces a form where it is legal: the hash form always is, the direct form up
+// to 1 GiB.  cn: the keys of the call's largest chunk.
+bool seq_direct(const bf_bank* b, uint64_t cn) {
+    if (b->seq_form == BF_BANK_SEQ_HASH || b->bytes > kSeqDirectMaxBytes) return false;
+    if (b->seq_form == BF_BANK_SEQ_DIRECT) return true;
+    return 4 * (b->bytes * 8) <= 12 * seq_slots(cn, b->k);
+}
+
+struct BankSeqCarve {
+    unsigned long long* tkeys;   // NULL: the direct form
+    uint32_t* tvals;
+    uint4* digests;
+    unsigned long long* cand;
+    uint64_t slots;
+};
+
+uint64_t seq_table_bytes(const bf_bank* b, bool direct, uint64_t cn) {
+    if (direct) return align256(b->bytes * 8 * 4);
+    const uint64_t slots = seq_slots(cn, b->k);
+    return align256(slots * 8) + align256(slots * 4);
+}
+
+uint64_t seq_scratch_bytes(const bf_bank* b, bool direct, uint64_t cn) {
+    return seq_table_bytes(b, direct, cn) + align256(cn * 16) + align256(cn * 8);
+}
+
+BankSeqCarve seq_carve(const bf_bank* b, bool direct, uint64_t cn) {
+    BankSeqCarve c{};
+    uint8_t* at = b->d_seq;
+    if (direct) {
+        c.slots = b->bytes * 8;
+        c.tvals = reinterpret_cast<uint32_t*>(at);
+    } else {
+        c.slots = seq_slots(cn, b->k);
+        c.tkeys = reinterpret_cast<unsigned long long*>(at);
+        c.tvals = reinterpret_cast<uint32_t*>(at + align256(c.slots * 8));
+    }
+    at += seq_table_bytes(b, direct, cn);
+    c.digests = reinterpret_cast<uint4*>(at);
+    at += align256(cn * 16);
+    c.cand = reinterpret_cast<unsigned long long*>(at);
+    return c;
+}
+
+// The scratch is the bank's and grows on demand.  An earlier call may still use the old buffer
+// on ITS stream (a _dev call on a caller's stream), so growth waits as bf_bank_sync does, not on
+// the bank's own stream only.
+int ensure_seq_scratch(bf_bank* b, uint64_t need) {
+    if (need <= b->seq_cap) return BF_OK;
+    HIPCHK(b, hipStreamSynchronize(b->stream));
+    if (b->order_valid) HIPCHK(b, hipEventSynchronize(b->order_ev));
+    if (b->d_seq) (void)hipFree(b->d_seq);
+    b->d_seq = nullptr;
+    b->seq_cap = 0;
+    HIPCHK(b, hipMalloc((void**)&b->d_seq, need));
+    b->seq_cap = need;
+    return BF_OK;
+}
+
+// One chunk of at most bf_seq_chunk_keys(k) keys: clear, candidates, mark, in stream order.
+int launch_seq_chunk(bf_bank* b, bool direct, const uint8_t* d_keys, const uint64_t* d_off, const uint32_t* d_ids,
+                     uint64_t cn, uint8_t* d_out8, hipStream_t s) {
+    const BankSeqCarve c = seq_carve(b, direct, cn);
+    if (c.tkeys) HIPCHK(b, hipMemsetAsync(c.tkeys, 0, c.slots * 8, s));
+    HIPCHK(b, hipMemsetAsync(c.tvals, 0xFF, c.slots * 4, s));
+    uint64_t bias = 0;
+    const uint8_t* k16 = align_keys(d_keys, &bias);
+    const dim3 grid((uint32_t)((cn + kBankTile - 1) / kBankTile)), block(kBankTile);
+    const uint64_t sw = b->stride / 4;
+    if (direct) {
+        hipLaunchKernelGGL(bank_seq_candidates_kernel<true>, grid, block, 0, s, b->g, b->n_filters, sw, k16, d_off, bias,
+                           d_ids, cn, c.tkeys, c.tvals, 0, c.digests, c.cand, b->d_status);
+        hipLaunchKernelGGL(bank_seq_mark_kernel<true>, grid, block, 0, s, b->g, sw, d_ids, cn, c.tkeys, c.tvals, 0,
+                           c.digests, c.cand, d_out8);
+    } else {
+        hipLaunchKernelGGL(bank_seq_candidates_kernel<false>, grid, block, 0, s, b->g, b->n_filters, sw, k16, d_off, bias,
+                           d_ids, cn, c.tkeys, c.tvals, c.slots - 1, c.digests, c.cand, b->d_status);
+        hipLaunchKernelGGL(bank_seq_mark_kernel<false>, grid, block, 0, s, b->g, sw, d_ids, cn, c.tkeys, c.tvals,
+                           c.slots - 1, c.digests, c.cand, d_out8);
+    }
+    HIPCHK(b, hipGetLastError());
+    return BF_OK;
 }
 
 // ids == NULL lists every filter in order; then count must be n_filters.
@@ -1140,7 +1378,7 @@ int bf_bank_destroy(bf_bank* b) {
         (void)hipStreamSynchronize(b->stream);
         if (b->order_valid) (void)hipEventSynchronize(b->order_ev);
         for (void* p : {(void*)b->g.bits, (void*)b->d_keys, (void*)b->d_out, (void*)b->d_off, (void*)b->d_ids,
-                        (void*)b->d_io, (void*)b->d_list})
+                        (void*)b->d_io, (void*)b->d_list, (void*)b->d_seq})
             if (p) (void)hipFree(p);
         if (b->order_ev) (void)hipEventDestroy(b->order_ev);
         if (b->h_status) (void)hipHostFree(b->h_status);
@@ -1203,6 +1441,87 @@ int bf_bank_insert_many_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64
 int bf_bank_include_many_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets,
                              const uint32_t* d_filter_ids, uint64_t n, uint8_t* d_out, void* stream) {
     return run_dev(b, BANK_INCLUDE, d_key_bytes, d_offsets, d_filter_ids, n, d_out, stream);
+}
+
+int bf_bank_set_seq_form(bf_bank* b, uint32_t form) {
+    if (!b) return BF_EINVAL;
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (form != BF_BANK_SEQ_AUTO && form != BF_BANK_SEQ_HASH && form != BF_BANK_SEQ_DIRECT)
+        return bank_err(b, BF_EINVAL, "unknown form %u", form);
+    b->seq_form = form;
+    return BF_OK;
+}
+
+int bf_bank_seq_plan(const bf_bank* b, uint64_t n, uint32_t* direct, uint64_t* chunk_keys, uint64_t* scratch_bytes) {
+    if (!b) return BF_EINVAL;
+    const uint64_t cn = std::min<uint64_t>(n, bf_seq_chunk_keys(b->k));
+    const bool d = seq_direct(b, cn);
+    if (direct) *direct = d ? 1u : 0u;
+    if (chunk_keys) *chunk_keys = cn;
+    if (scratch_bytes) *scratch_bytes = cn ? seq_scratch_bytes(b, d, cn) : 0;
+    return BF_OK;
+}
+
+int bf_bank_insert_many_seq(bf_bank* b, const uint8_t* key_bytes, const uint64_t* offsets, const uint32_t* filter_ids,
+                            uint64_t n, uint8_t* per_key_new) {
+    if (!b) return BF_EINVAL;
+    if (n == 0) return BF_OK;
+    CallScope cs(b);
+    int rc = check_batch(b, key_bytes, offsets, filter_ids, n);
+    if (rc) return rc;
+    if (int orc = cs.open(b->stream)) return orc;
+    // the form is the call's (bf_bank_seq_plan); run_host's chunks, bounded again by the index width
+    const uint64_t seq_chunk = bf_seq_chunk_keys(b->k);
+    const bool direct = seq_direct(b, std::min<uint64_t>(n, seq_chunk));
+    const uint64_t max_keys = std::min<uint64_t>(b->batch_keys, seq_chunk);
+    if ((rc = ensure_seq_scratch(b, seq_scratch_bytes(b, direct, std::min<uint64_t>(n, max_keys))))) return rc;
+    std::vector<uint64_t> rebased;
+    uint64_t a = 0;
+    while (a < n) {
+        uint64_t e = std::min<uint64_t>(n, a + max_keys);
+        if (offsets[e] - offsets[a] > b->batch_bytes) {
+            e = (uint64_t)(std::upper_bound(offsets + a, offsets + e + 1, offsets[a] + b->batch_bytes) - offsets) - 1;
+            if (e <= a) e = a + 1;
+        }
+        const uint64_t cn = e - a, nbytes = offsets[e] - offsets[a];
+        if ((rc = ensure_keys_io(b, nbytes, cn))) return rc;
+        rebased.resize(cn + 1);
+        for (uint64_t j = 0; j <= cn; ++j) rebased[j] = offsets[a + j] - offsets[a];
+        if (nbytes) HIPCHK(b, hipMemcpyAsync(b->d_keys, key_bytes + offsets[a], nbytes, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(b, hipMemsetAsync(b->d_keys + nbytes, 0, 16, b->stream));
+        HIPCHK(b, hipMemcpyAsync(b->d_off, rebased.data(), (cn + 1) * 8, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(b, hipMemcpyAsync(b->d_ids, filter_ids + a, cn * 4, hipMemcpyHostToDevice, b->stream));
+        if ((rc = launch_seq_chunk(b, direct, b->d_keys, b->d_off, b->d_ids, cn, per_key_new ? b->d_out : nullptr,
+                                   b->stream)))
+            return rc;
+        if (per_key_new) HIPCHK(b, hipMemcpyAsync(per_key_new + a, b->d_out, cn, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(b, hipStreamSynchronize(b->stream));   // the staging buffers and `rebased` are free again
+        a = e;
+    }
+    return BF_OK;
+}
+
+int bf_bank_insert_many_seq_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets,
+                                const uint32_t* d_filter_ids, uint64_t n, uint8_t* d_per_key_new, void* stream) {
+    if (!b) return BF_EINVAL;
+    if (n == 0) return BF_OK;
+    CallScope cs(b);
+    if (!d_key_bytes || !d_offsets || !d_filter_ids) return bank_err(b, BF_EINVAL, "NULL device pointer");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (int orc = cs.open(s)) return orc;
+    const uint64_t chunk = bf_seq_chunk_keys(b->k);
+    const bool direct = seq_direct(b, std::min<uint64_t>(n, chunk));
+    // synchronises only when the scratch has to grow
+    int rc = ensure_seq_scratch(b, seq_scratch_bytes(b, direct, std::min<uint64_t>(n, chunk)));
+    if (rc) return rc;
+    // offsets[0] need not be 0, so d_offsets + a is the offsets array of the keys from a on
+    for (uint64_t a = 0; a < n; a += chunk) {
+        const uint64_t cn = std::min<uint64_t>(n - a, chunk);
+        if ((rc = launch_seq_chunk(b, direct, d_key_bytes, d_offsets + a, d_filter_ids + a, cn,
+                                   d_per_key_new ? d_per_key_new + a : nullptr, s)))
+            return rc;
+    }
+    return BF_OK;
 }
 
 int bf_bank_across_row_bytes(uint64_t count, uint64_t* bytes) {

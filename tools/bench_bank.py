@@ -37,6 +37,16 @@ each timed roll-up its destinations are cleared (untimed), so every vector is st
 every bit set with probability 1/2.
 
     python tools/bench_bank.py --combine [--only small|many|big] [--runs 25] [--out profiles/bank_combine.json]
+
+--seq times the insert with exact sequential per-key flags (bf_bank_insert_many_seq_dev) on the
+first workload (2^22 keys, random ids, 10^3 and 10^5 filters, a cleared bank before every run)
+against (b) bf_bank_insert_many_dev on the same keys, include?-then-insert through the two *_dev
+calls (approximate answers) and, for 10^3 filters, (c) the one way there was to get the same
+flags: the keys grouped by id through 10^3 ``Filter`` handles' ``insert_many_dev`` with
+``d_per_key_new``.  Where the bank picks the direct table the forced hash form is timed too.  The
+flags of (a) and (c) and the bits of all of them are compared once outside the timed region.
+
+    python tools/bench_bank.py --seq [--filters 1000,100000] [--runs 25] [--out profiles/bank_seq.json]
 """
 import argparse
 import json
@@ -162,6 +172,95 @@ def run_bank(pkg, m, k, nf, n, buf, offs, runs, warmup) -> dict:
         res["speedup_include_vs_handles"] = round(res["handles_include"]["ms"] / res["include"]["ms"], 1)
     res["insert_vs_flat"] = round(res["flat_insert"]["ms"] / res["insert"]["ms"], 2)
     res["include_vs_flat"] = round(res["flat_include"]["ms"] / res["include"]["ms"], 2)
+    return res
+
+
+# ---- --seq: the insert with exact sequential flags against the plain insert and the handles ------
+
+def run_seq(pkg, m, k, nf, n, buf, offs, runs, warmup) -> dict:
+    """run_bank's workload through bf_bank_insert_many_seq_dev (a), against bf_bank_insert_many_dev
+    on the same keys (b), include?-then-insert (approximate answers: two copies of a pair inside
+    the batch both read "not seen") and, up to HANDLES_MAX filters, the one way there was to get
+    the same flags (c): the keys grouped by id through one ``Filter`` handle each,
+    ``insert_many_dev`` with ``d_per_key_new``.  Every insert starts from cleared filters."""
+    ids = np.random.default_rng([0xBA2C, nf]).integers(0, nf, n).astype(np.uint32)
+    dk, do, di = to_dev(buf, offs, ids)
+    flags = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    out8 = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    res = {"n_filters": nf}
+
+    def time_bank(bank):
+        args = (dk.data_ptr(), do.data_ptr(), di.data_ptr(), n)
+        clear = lambda: bank.clear_dev(stream=0)   # noqa: E731
+        t = {"seq": entry(timed_events(lambda: bank.insert_many_seq_dev(*args, flags.data_ptr(), stream=0), runs, warmup,
+                                       before=clear), n)}
+        torch.cuda.synchronize()
+        bank.sync()
+        t["set_bits"], t["new_keys"] = int(bank.bitcount().sum()), int(flags.sum())
+        return t
+
+    with pkg.FilterBank(m, k, nf, device=0) as bank:
+        res["stride"], res["device_bytes"] = bank.stride, bank.device_bytes
+        direct, chunk, scratch = bank.seq_plan(n)
+        res["plan"] = {"form": "direct" if direct else "hash", "chunk_keys": chunk, "scratch_bytes": scratch}
+        t = time_bank(bank)
+        res["seq"], res["set_bits"], res["new_keys"] = t["seq"], t["set_bits"], t["new_keys"]
+        bank_flags = flags.cpu().numpy()
+        args = (dk.data_ptr(), do.data_ptr(), di.data_ptr(), n)
+        clear = lambda: bank.clear_dev(stream=0)   # noqa: E731
+        res["insert"] = entry(timed_events(lambda: bank.insert_many_dev(*args, stream=0), runs, warmup, before=clear), n)
+        torch.cuda.synchronize()
+        assert int(bank.bitcount().sum()) == res["set_bits"], "the two inserts leave different bits"
+
+        def include_then_insert():
+            bank.include_many_dev(*args, out8.data_ptr(), stream=0)
+            bank.insert_many_dev(*args, stream=0)
+
+        res["include_then_insert"] = entry(timed_events(include_then_insert, runs, warmup, before=clear), n)
+        torch.cuda.synchronize()
+        bank.sync()
+        # on distinct keys into cleared filters include?-before-insert of the whole batch is all 0
+        assert not bool(out8.any())
+
+    if direct:   # the other form on the same bank, forced
+        with pkg.FilterBank(m, k, nf, device=0) as bank:
+            bank.set_seq_form("hash")
+            assert bank.seq_plan(n)[0] is False
+            t = time_bank(bank)
+        assert (t["set_bits"], t["new_keys"]) == (res["set_bits"], res["new_keys"])
+        assert np.array_equal(flags.cpu().numpy(), bank_flags), "the two forms differ"
+        res["seq_hash_forced"] = t["seq"]
+
+    if nf <= HANDLES_MAX:
+        order = np.argsort(ids, kind="stable")
+        sorted_buf = np.concatenate([buf[:-16].reshape(n, KEY_BYTES)[order].reshape(-1), np.zeros(16, np.uint8)])
+        starts = np.searchsorted(ids[order], np.arange(nf + 1), side="left")
+        sk, so = to_dev(sorted_buf, offs)
+        filters = [pkg.Filter(m, k, device=0) for _ in range(nf)]
+        spans = [(f, so.data_ptr() + 8 * int(starts[i]), int(starts[i + 1] - starts[i]), int(starts[i]))
+                 for i, f in enumerate(filters) if starts[i + 1] > starts[i]]
+
+        def handles_loop():
+            for f, d_off, cnt, first in spans:
+                f.insert_many_dev(sk.data_ptr(), d_off, cnt, d_per_key_new=flags.data_ptr() + first, stream=0)
+
+        def clear_all():
+            for f in filters:
+                f.clear()
+
+        res["handles_seq"] = entry(timed_events(handles_loop, runs, warmup, before=clear_all), n)
+        torch.cuda.synchronize()
+        # the same answers: a stable sort keeps each filter's keys in batch order
+        assert np.array_equal(flags.cpu().numpy(), bank_flags[order]), "the handles' flags differ from the bank's"
+        assert sum(f.bitcount() for f in filters) == res["set_bits"]
+        for f in filters:
+            f.close()
+        res["handles_over_seq"] = round(res["handles_seq"]["ms"] / res["seq"]["ms"], 2)
+    res["seq_over_insert"] = round(res["seq"]["ms"] / res["insert"]["ms"], 2)
+    res["seq_over_include_then_insert"] = round(res["seq"]["ms"] / res["include_then_insert"]["ms"], 2)
+    print("%d filters: seq %.3f ms, insert %.3f ms, include+insert %.3f ms%s" % (
+        nf, res["seq"]["ms"], res["insert"]["ms"], res["include_then_insert"]["ms"],
+        ", handles %.3f ms" % res["handles_seq"]["ms"] if "handles_seq" in res else ""), file=sys.stderr, flush=True)
     return res
 
 
@@ -438,6 +537,9 @@ def main():
                     help="time the cross query against the crossed batch instead (profiles/bank_across.json)")
     ap.add_argument("--combine", action="store_true",
                     help="time folds and the overlap matrix against export + numpy + import (profiles/bank_combine.json)")
+    ap.add_argument("--seq", action="store_true",
+                    help="time the insert with sequential flags against the plain insert and the handles "
+                         "(profiles/bank_seq.json)")
     ap.add_argument("--only", choices=["small", "many", "big"], default=None,
                     help="--combine: the shapes of one bank only (10^3 filters, 10^4 filters, 5 x 120 MB)")
     args = ap.parse_args()
@@ -471,6 +573,17 @@ def main():
         return
     n = 1 << args.log2_keys
     buf, offs = decimal_keys(n)
+    if args.seq:
+        doc = {"tool": "tools/bench_bank.py --seq", "device": torch.cuda.get_device_name(0), "m": m, "k": k, "keys": n,
+               "key_bytes": KEY_BYTES, "runs": args.runs, "warmup": args.warmup,
+               "banks": {str(nf): run_seq(pkg, m, k, int(nf), n, buf, offs, args.runs, args.warmup)
+                         for nf in args.filters.split(",")}}
+        line = json.dumps(doc)
+        print(line)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     doc = {"tool": "tools/bench_bank.py", "device": torch.cuda.get_device_name(0), "m": m, "k": k, "keys": n,
            "key_bytes": KEY_BYTES, "runs": args.runs, "warmup": args.warmup,
            "banks": {str(nf): run_bank(pkg, m, k, int(nf), n, buf, offs, args.runs, args.warmup)
