@@ -35,6 +35,7 @@
  *   bf_estimate_count  distinct keys behind a bit count, under the probe law of        ruby.rb:51
  *   bf_bank_*          many filters of one (m, k), one per key_name, behind one handle:
  *                      Ruby#insert / #include? / #clear per (key_name, key)     ruby.rb:15-35, 57-63
+ *                      (bf_bank_insert_many_changes: with the bits it set, for a SETBIT write-through)
  *                      and #include? of one key in every listed key_name (bf_bank_include_across);
  *                      key_names combined with each other (bf_bank_fold, bf_bank_overlap)   ruby.rb:59, 61-62
  *   bf_optimal_m/_k    Redis::Bloomfilter.optimal_m / optimal_k       lib/redis/bloomfilter.rb:50-58
@@ -667,6 +668,41 @@ int  bf_lua_index(double entries, uint64_t count, uint32_t* layer);
  *                        wait of bf_bank_sync, without its report) ONLY when the scratch has to
  *                        grow, so a repeated shape never does.  Refusals are bf_bank_insert_many's
  *                        (_dev: bf_bank_insert_many_dev's; a skipped key reports 0).
+ *   bf_bank_insert_many_changes  the same insert, with the bits it set: what a write-through has   ruby.rb:57-63
+ *                        to replay as SETBIT key_name o 1 (ruby.rb:59).  Entry e of the list is the
+ *                        pair out_ids[e] (a filter id) and out_bits[e] (a bit offset WITHIN that
+ *                        filter, the SETBIT offset); two arrays, because an id and an offset do
+ *                        not fit 64 bits together for every legal shape.  The listed pairs are
+ *                        exactly the bits that are 1 after the call and were 0 before it, each
+ *                        once, in no particular order: where keys race for a bit, or two probes of
+ *                        one key name the same bit, the atomic's old value picks the one lane that
+ *                        lists it.  The bank's bits afterwards are exactly those
+ *                        bf_bank_insert_many leaves.  flags (nullable, n bytes): with seq = 0
+ *                        bf_bank_insert_many's key_flipped, with seq = 1
+ *                        bf_bank_insert_many_seq's per_key_new, then with that call's chunks,
+ *                        scratch, growth rule and bf_bank_set_seq_form.  *count = the number of
+ *                        flipped bits: *count > 0 is "some string changed", and the distinct
+ *                        out_ids are exactly the key_names whose string changed (the reference's
+ *                        !found per key_name).  *count > cap: the host form returns BF_ERANGE
+ *                        AFTER the insert is fully applied, as bf_lua_insert_many_changes does;
+ *                        flags are complete, *count is the true total and the first cap entries
+ *                        are distinct, genuinely flipped bits.  cap == 0 allows NULL lists (the
+ *                        count only); cap >= n * k always suffices.  n == 0: BF_OK, *count = 0.
+ *                        There is no bound on n * k as in bf_insert_many_changes: list slots are
+ *                        reserved once per 256 keys, not once per bit.  The host form refuses
+ *                        (BF_EINVAL; nothing launched, outputs and bank untouched) a NULL b or
+ *                        count, seq > 1, cap > 0 with a NULL list and what bf_bank_insert_many
+ *                        refuses.  It runs in cfg's batch_keys / batch_bytes chunks whose lists are
+ *                        concatenated into the caller's arrays; the device list scratch is the
+ *                        bank's, grows on demand and never holds more than min(cap, chunk keys *
+ *                        k) entries.  The _dev form zeroes *d_count (8 bytes) on the stream and
+ *                        its kernels add to it, every chunk of a sequential call to the same
+ *                        counter; it does not synchronise (but for the sequential scratch growth
+ *                        of bf_bank_insert_many_seq_dev) and returns no BF_ERANGE: the caller
+ *                        compares *d_count with cap.  It refuses NULL or misaligned pointers
+ *                        (d_out_bits, d_count: 8 bytes; d_out_ids: 4; the lists may be NULL only
+ *                        with cap == 0; keys, offsets and ids as bf_bank_insert_many_dev) and seq
+ *                        > 1; a key its kernel skips (below) lists nothing.
  *   bf_bank_set_seq_form forces the table's form for the bank's later calls where it is legal
  *                        (BF_BANK_SEQ_HASH: always; BF_BANK_SEQ_DIRECT: up to 2^28 bits of bank;
  *                        BF_BANK_SEQ_AUTO, the default: the bank's own rule).  It never changes a
@@ -784,6 +820,15 @@ int  bf_bank_insert_many_seq(bf_bank* b, const uint8_t* key_bytes, const uint64_
 int  bf_bank_insert_many_seq_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets,
                                  const uint32_t* d_filter_ids, uint64_t n, uint8_t* d_per_key_new /* nullable */,
                                  void* stream);
+/* entry e of the list: bit out_bits[e] of filter out_ids[e] went 0 -> 1 */
+int  bf_bank_insert_many_changes(bf_bank* b, const uint8_t* key_bytes, const uint64_t* offsets,
+                                 const uint32_t* filter_ids, uint64_t n, uint32_t seq /* 0 | 1 */,
+                                 uint8_t* flags /* nullable, n bytes */, uint32_t* out_ids, uint64_t* out_bits,
+                                 uint64_t cap, uint64_t* count);
+int  bf_bank_insert_many_changes_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets,
+                                     const uint32_t* d_filter_ids, uint64_t n, uint32_t seq,
+                                     uint8_t* d_flags /* nullable */, uint32_t* d_out_ids, uint64_t* d_out_bits,
+                                     uint64_t cap, uint64_t* d_count /* 8 bytes, 8-byte aligned */, void* stream);
 #define BF_BANK_SEQ_AUTO   0u
 #define BF_BANK_SEQ_HASH   1u
 #define BF_BANK_SEQ_DIRECT 2u

@@ -169,6 +169,8 @@ SIGNATURES = {
     "bf_bank_insert_many_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
     "bf_bank_insert_many_seq": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "bf_bank_insert_many_seq_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "bf_bank_insert_many_changes": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _u64, _u64p]),
+    "bf_bank_insert_many_changes_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _vp]),
     "bf_bank_set_seq_form": (ctypes.c_int, [_vp, _u32]),
     "bf_bank_seq_plan": (ctypes.c_int, [_vp, _u64, _u32p, _u64p, _u64p]),
     "bf_bank_include_many": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
@@ -944,6 +946,27 @@ class FilterBank(_Handle):
                     self._h)
         return new[:n]
 
+    def insert_many_changes(self, keys: np.ndarray, offsets: np.ndarray, filter_ids: np.ndarray, seq: bool = False,
+                            cap: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``insert_many`` (``seq=True``: ``insert_many_seq``) that also lists the bits it flipped
+        0 -> 1 (bf_bank_insert_many_changes).  Returns ``(flags, ids, bits)``: that insert's per-key
+        flags, and the list as two arrays, bit ``bits[e]`` (uint64, the SETBIT offset of ruby.rb:59)
+        of filter ``ids[e]`` (uint32); each flipped bit once, in no particular order.  ``cap``
+        bounds the list and defaults to n * k, which always suffices; when the batch flips more
+        bits than an explicit ``cap`` the insert is still applied and ArgumentError (BF_ERANGE)
+        raised."""
+        keys, offsets, fids, n = self._batch(keys, offsets, filter_ids)
+        cap = n * self.k if cap is None else int(cap)
+        if not 0 <= cap < 1 << 64:
+            raise ArgumentError("cap must be an unsigned 64-bit integer, got %r" % (cap,))
+        flags = np.zeros(max(n, 1), np.uint8)
+        ids, bits = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint64)
+        count = ctypes.c_uint64()
+        _bank_check(self._lib.bf_bank_insert_many_changes(self.handle, _ptr(keys), _ptr(offsets), _ptr(fids), n,
+                                                          1 if seq else 0, _ptr(flags), _ptr(ids), _ptr(bits), cap,
+                                                          ctypes.byref(count)), self._h)
+        return flags[:n], ids[:count.value], bits[:count.value]
+
     def seq_plan(self, n: int) -> Tuple[bool, int, int]:
         """How ``insert_many_seq*`` runs a batch of ``n`` keys, without a launch: (direct: the
         first-index table is one word per bit of the bank, not a hash table; keys per chunk; bytes
@@ -1099,6 +1122,19 @@ class FilterBank(_Handle):
         grow (the first call of a shape; see ``seq_plan``)."""
         _bank_check(self._lib.bf_bank_insert_many_seq_dev(self.handle, d_keys, d_offsets, d_filter_ids, int(n),
                                                           d_per_key_new or None, self._s(stream)), self._h)
+
+    def insert_many_changes_dev(self, d_keys: int, d_offsets: int, d_filter_ids: int, n: int, d_count: int,
+                                d_out_ids: int = 0, d_out_bits: int = 0, cap: int = 0, seq: bool = False,
+                                d_flags: int = 0, stream=None) -> None:
+        """``insert_many_changes`` on device arrays (bf_bank_insert_many_changes_dev): the uint64 at
+        d_count (8-byte aligned) is zeroed on ``stream`` and then counts every flipped bit; the first
+        ``cap`` of them are listed at d_out_ids (uint32) and d_out_bits (uint64, 8-byte aligned),
+        which may be 0 with ``cap=0``.  An overflow is not an error here: compare the count with
+        ``cap``.  ``seq`` is passed as given (0 / 1)."""
+        _bank_check(self._lib.bf_bank_insert_many_changes_dev(self.handle, d_keys or None, d_offsets or None,
+                                                              d_filter_ids or None, int(n), int(seq), d_flags or None,
+                                                              d_out_ids or None, d_out_bits or None, int(cap),
+                                                              d_count or None, self._s(stream)), self._h)
 
     def include_many_dev(self, d_keys: int, d_offsets: int, d_filter_ids: int, n: int, d_out: int,
                          stream=None) -> None:

@@ -20,6 +20,13 @@ Redis sync follows ``drivers/hip.py``'s contract, per key name:
   written back, its trimmed string with ``SETRANGE name 0`` (keeps the TTL; under OR a string
   only grows, so the key becomes exactly the string the ruby driver's SETBITs build), followed
   by EXPIRE when ``expire`` is given — ruby.rb:61-62, per key name;
+* ``sync='write_through_bits'``: the same, but an insert asks the device WHICH bits it flipped
+  (bf_bank_insert_many_changes) and a key name that changed by only a few bits gets exactly the
+  SETBITs the ruby driver would have sent that changed something (ruby.rb:58-60) instead of its
+  whole string: ``bank[name].insert(key)`` then sends at most k SETBITs, not ceil(m / 8) bytes.
+  A key name with more flipped bits than k and than ``ceil(m / 8) / SETBIT_BYTES`` (the hip
+  driver's cost model) is written whole as above.  A SETBIT keeps the TTL and grows the string as the
+  reference's does, so Redis ends byte for byte where the default mode leaves it;
 * ``sync='manual'``: Redis is touched only by ``flush`` / ``reload`` / ``clear``;
 * TTL: when a key name's mirrored deadline passes, that one filter is cleared, as the Redis key
   would have vanished.
@@ -35,6 +42,7 @@ from . import fakeredis
 from . import keys as _keys
 from ._lib import ArgumentError, BF_IMPORT_REPLACE, FilterBank, estimate_count
 from .bloomfilter import Bloomfilter
+from .drivers.hip import Hip
 
 
 class BankFilter:
@@ -59,7 +67,7 @@ class BankFilter:
 
 
 class BloomfilterBank:
-    SYNC_MODES = ("write_through", "manual")
+    SYNC_MODES = ("write_through", "manual", "write_through_bits")
 
     def __init__(self, size=None, error_rate=None, key_names: Optional[Sequence] = None, redis=None,
                  sync: str = "write_through", default_expire=None, device: int = -1, clock=time.monotonic):
@@ -122,7 +130,7 @@ class BloomfilterBank:
             del self._deadline[i]
             self._dirty.discard(i)
             self._replaced.discard(i)
-            if self.redis is not None and self.sync_mode == "write_through":
+            if self.redis is not None and self.sync_mode != "manual":
                 self.redis.delete(self.key_names[i])
 
     def _write(self, ids: Sequence[int]) -> int:
@@ -143,18 +151,56 @@ class BloomfilterBank:
         changed (the reference's ``!found`` per key name)."""
         self._expired()
         ids, buf, offs = self._batch(names, keys)
+        if self.sync_mode == "write_through_bits":
+            _, lids, lbits = self.bank.insert_many_changes(buf, offs, ids)
+            return self._inserted(lids, None, expire, lbits)
         flipped = self.bank.insert_many(buf, offs, ids)
         return self._inserted(ids, flipped, expire)
 
-    def _inserted(self, ids: np.ndarray, new: np.ndarray, expire) -> Set[str]:
-        """The Redis side of an insert, per key name whose string changed (``ids[new != 0]``):
-        write-through SETRANGE or dirty marking, EXPIRE and deadline arming (ruby.rb:61-62).
+    # One SETBIT costs the server about as much as SETRANGEing this many bytes: the hip driver's
+    # cost model and its one constant (drivers/hip.py).
+    SETBIT_BYTES = Hip.SETBIT_BYTES
+
+    def _write_bits(self, lids: np.ndarray, lbits: np.ndarray) -> None:
+        """``write_through_bits``: per changed key name, the flipped bits as SETBIT name o 1
+        (ruby.rb:58-60; pipelined when the client can) while they cost less than the string
+        ``_write`` would send, else that string.  ceil(m / 8) bounds the string, so no filter is
+        exported just to decide.  As in the hip driver, what a per-key call can flip (k bits, no
+        more than the reference's own k SETBITs for that key) is always replayed."""
+        order = np.argsort(lids, kind="stable")
+        lids, lbits = lids[order], lbits[order]
+        names, starts = np.unique(lids, return_index=True)
+        ends = list(starts[1:]) + [len(lids)]
+        string_bytes = -(-self.options["bits"] // 8)
+        k = self.options["hashes"]
+        whole, replay = [], []
+        for i, s, e in zip(names.tolist(), starts.tolist(), ends):
+            if e - s <= k or (e - s) * self.SETBIT_BYTES <= string_bytes:
+                replay.append((self.key_names[i], lbits[s:e].tolist()))
+            else:
+                whole.append(i)
+        if replay:
+            pipe = getattr(self.redis, "pipeline", None)
+            r = pipe(transaction=False) if pipe is not None else self.redis
+            for name, offsets in replay:
+                for o in offsets:
+                    r.setbit(name, o, 1)
+            if pipe is not None:
+                r.execute()
+        self._write(whole)
+
+    def _inserted(self, ids: np.ndarray, new: Optional[np.ndarray], expire, bits: Optional[np.ndarray] = None) -> Set[str]:
+        """The Redis side of an insert, per key name whose string changed (``ids[new != 0]``; with
+        ``bits``, the list of bf_bank_insert_many_changes: its distinct ids): write-through
+        SETRANGE / SETBITs or dirty marking, EXPIRE and deadline arming (ruby.rb:61-62).
         Returns those key names."""
-        changed = sorted(set(ids[new != 0].tolist()))
+        changed = sorted(set((ids if bits is not None else ids[new != 0]).tolist()))
         expire = self._expire(expire)
         armed = expire is not None and expire is not False   # ruby.rb:62: 0 counts
-        write = self.redis is not None and self.sync_mode == "write_through"
-        if write:
+        write = self.redis is not None and self.sync_mode != "manual"
+        if write and bits is not None:
+            self._write_bits(ids, bits)
+        elif write:
             self._write(changed)
         else:
             self._dirty.update(changed)
@@ -177,8 +223,12 @@ class BloomfilterBank:
         Towards Redis it behaves like ``insert_many``."""
         self._expired()
         ids, buf, offs = self._batch(names, keys)
-        new = self.bank.insert_many_seq(buf, offs, ids)
-        self._inserted(ids, new, expire)
+        if self.sync_mode == "write_through_bits":
+            new, lids, lbits = self.bank.insert_many_changes(buf, offs, ids, seq=True)
+            self._inserted(lids, None, expire, lbits)
+        else:
+            new = self.bank.insert_many_seq(buf, offs, ids)
+            self._inserted(ids, new, expire)
         return new.astype(bool)
 
     def first_seen(self, name, key, expire=None) -> bool:
@@ -252,7 +302,7 @@ class BloomfilterBank:
         d = self._id(dst)
         changed = bool(self.bank.fold("or", [[d] + [self._id(n) for n in sources]], [d])[0][0])
         if changed:
-            write = self.redis is not None and self.sync_mode == "write_through"
+            write = self.redis is not None and self.sync_mode != "manual"
             if write:
                 self._write([d])
             else:
@@ -272,7 +322,7 @@ class BloomfilterBank:
             raise ArgumentError("rollup needs at least one source key name")
         changed, set_bits = self.bank.fold("or", [srcs], [d])
         if changed[0]:
-            write = self.redis is not None and self.sync_mode == "write_through"
+            write = self.redis is not None and self.sync_mode != "manual"
             self._deadline.pop(d, None)
             if write:
                 self.redis.delete(self.key_names[d])

@@ -16,6 +16,9 @@
 //                       from bf_device.h, the k probes inside the lane's own filter.
 //   bank_seq_*_kernel   insert with the exact sequential per-key flag (first-seen dedup): bf_seq.hip's
 //                       candidates / mark pair, the first-index table keyed by the bank-wide bit.
+//   bank_list_tile      bf_bank_insert_many_changes*: the LIST instantiations of the two insert
+//                       kernels also list every bit their own atomics flipped, as (filter id,
+//                       SETBIT offset) pairs; slots reserved once per workgroup.
 //   bank_across_kernel  include? of one key in many filters: the same tile, hashed once per
 //                       workgroup, its k bit positions tested in every filter of a chunk of the
 //                       list; one 64-entry mask word per lane and group.
@@ -55,19 +58,86 @@ thread_local std::string g_bank_create_error;
 
 enum : int { BANK_INSERT = 0, BANK_INCLUDE = 1 };
 
+// ---- the list of flipped bits (bf_bank_insert_many_changes*) -----------------------------------
+
+// Where an insert kernel lists the bits it flipped 0 -> 1: entry e is the pair (ids[e], bits[e]) =
+// (filter, SETBIT offset within it, ruby.rb:59).  *count counts every flipped bit of the call;
+// an entry at or past cap is counted and not written.  BankList<false> is empty: the kernels of
+// the entry points without a list are instantiated without any of it.
+template <bool LIST>
+struct BankList {};
+template <>
+struct BankList<true> {
+    uint32_t* ids;
+    uint64_t* bits;
+    uint64_t cap;
+    unsigned long long* count;
+};
+
+// A workgroup of kBankTile lanes lists its flipped probes.  fm is the lane's mask of them (probe
+// i: bit i; k <= BF_MAX_K = 64, as cand below), 0 for a lane without a key.  Slots are reserved
+// per workgroup, not per bit: the popcounts' prefix sum over the wave by shuffles and over the
+// waves through LDS, then ONE returning add on the counter (none for a tile that flipped
+// nothing), and every lane writes its entries from its own base, the offsets derived again from
+// the digest.  One contended word takes about 88 returning atomics per microsecond: an add per
+// flipped bit would serialise a batch of 2^22 keys for tens of milliseconds, an add per tile
+// for about 0.2.  Every lane of the workgroup calls this once (two barriers).
+__device__ __forceinline__ void bank_list_tile(const BfGeom& g, const BankList<true>& list, unsigned long long fm,
+                                               uint32_t id, uint32_t h0, uint32_t h1, uint32_t h2, uint32_t h3) {
+    __shared__ unsigned long long s_base[kBankTile / 64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t mine = (uint32_t)__popcll(fm);
+    uint32_t incl = mine;   // inclusive prefix sum over the wave
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(incl, d);
+        if (lane >= d) incl += y;
+    }
+    if (lane == 63u) s_base[wave] = incl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long part[kBankTile / 64], total = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < kBankTile / 64; ++w) {
+            part[w] = total;
+            total += s_base[w];
+        }
+        const unsigned long long base =
+            total ? __hip_atomic_fetch_add(list.count, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+#pragma unroll
+        for (uint32_t w = 0; w < kBankTile / 64; ++w) s_base[w] = base + part[w];
+    }
+    __syncthreads();
+    unsigned long long e = s_base[wave] + (incl - mine);
+    while (fm) {
+        const uint32_t i = (uint32_t)__builtin_ctzll(fm);
+        fm &= fm - 1;
+        if (e < list.cap) {
+            list.ids[e] = id;
+            list.bits[e] = probe_offset(g, h0, h1, h2, h3, i);
+        }
+        ++e;
+    }
+}
+
 // status[0]: a key's offsets failed bfdev::key_ok; status[1]: a filter id >= n_filters.
 // Both live in the bank's pinned status block, which bf_bank_sync reports.
-template <int OP>
+// LIST (insert only): every bit a lane's own atomic flipped goes to `list` (bank_list_tile).
+template <int OP, bool LIST = false>
 __global__ __launch_bounds__(kBankTile) void bank_keys_kernel(BfGeom g, uint64_t n_filters, uint64_t stride_words,
                                                               const uint8_t* __restrict__ keys16,
                                                               const uint64_t* __restrict__ offsets, uint64_t bias,
                                                               const uint32_t* __restrict__ ids, uint64_t n,
                                                               uint8_t* __restrict__ out8,
-                                                              uint32_t* __restrict__ status) {
+                                                              uint32_t* __restrict__ status, BankList<LIST> list) {
+    static_assert(!LIST || OP == BANK_INSERT, "only an insert flips bits");
     __shared__ uint64_t s_off[kBankTile + 1];
     __shared__ uint4 s_stage[kBankStageVec + kStageSlackVec];
     const uint64_t tile0 = (uint64_t)blockIdx.x * kBankTile;
     const uint32_t cnt = (uint32_t)((n - tile0) < (uint64_t)kBankTile ? (n - tile0) : kBankTile);
+    // LIST: what the lane lists after the tile; a lane without a key, or with a refused one, keeps 0
+    [[maybe_unused]] unsigned long long fm = 0;
+    [[maybe_unused]] uint32_t fid = 0, fh[4] = {0u, 0u, 0u, 0u};
     for_key_tile<kBankTile, kBankStageVec>(keys16, offsets, bias, tile0, cnt, s_off, s_stage, status,
         [&](auto staged, uint32_t lane, const uint32_t* src, uint32_t s, uint32_t L) {
             const uint64_t j = tile0 + lane;
@@ -131,12 +201,19 @@ __global__ __launch_bounds__(kBankTile) void bank_keys_kernel(BfGeom g, uint64_t
                             const uint32_t old = __hip_atomic_fetch_or(fb + w[c], mask[c], __ATOMIC_RELAXED,
                                                                        __HIP_MEMORY_SCOPE_AGENT);
                             flipped |= (old & mask[c]) ? 0u : 1u;
+                            if constexpr (LIST) fm |= (unsigned long long)((old & mask[c]) ? 0u : 1u) << (i0 + c);
                         }
                     }
                 }
                 if (out8) out8[j] = (uint8_t)flipped;
+                if constexpr (LIST) {
+                    fid = id;
+                    fh[0] = H[0]; fh[1] = H[1]; fh[2] = H[2]; fh[3] = H[3];
+                }
             }
         });
+    // after the tile, so that every lane of the workgroup, refused ones included, reaches the barriers
+    if constexpr (LIST) bank_list_tile(g, list, fm, fid, fh[0], fh[1], fh[2], fh[3]);
 }
 
 // ---- sequential per-key flags: the mixed batch inserted one pair at a time ---------------------
@@ -237,39 +314,50 @@ __global__ __launch_bounds__(kBankTile) void bank_seq_candidates_kernel(
 }
 
 // out8[j] (nullable) = new(j); every 0-probe of key j is ORed into its filter.
-template <bool DIRECT>
+// LIST: the probes whose atomicOr found the bit still 0 go to `list` (bank_list_tile): of the keys
+// of a chunk that probe one bit, and of one key's probes that name one bit, exactly one lists it.
+template <bool DIRECT, bool LIST = false>
 __global__ __launch_bounds__(kBankTile) void bank_seq_mark_kernel(
     BfGeom g, uint64_t stride_words, const uint32_t* __restrict__ ids, uint64_t n,
     const unsigned long long* __restrict__ tkeys, const uint32_t* __restrict__ tvals, uint64_t tmask,
-    const uint4* __restrict__ digests, const unsigned long long* __restrict__ cand, uint8_t* __restrict__ out8) {
+    const uint4* __restrict__ digests, const unsigned long long* __restrict__ cand, uint8_t* __restrict__ out8,
+    BankList<LIST> list) {
     const uint64_t j = (uint64_t)blockIdx.x * kBankTile + threadIdx.x;
-    if (j >= n) return;
-    uint32_t isnew = 0;
-    unsigned long long cm = cand[j];
-    if (cm) {   // a key with a 0-probe passed the candidates' checks: its id is in range
-        const uint4 H = digests[j];
-        const uint64_t id = ids[j];
-        uint32_t* __restrict__ fb = g.bits + id * stride_words;
-        const uint64_t bit0 = id * stride_words * 32u;
-        while (cm) {
-            const uint32_t i = (uint32_t)__builtin_ctzll(cm);
-            cm &= cm - 1;
-            const uint64_t o = probe_offset(g, H.x, H.y, H.z, H.w, i);
-            const uint64_t bn = bit0 + o;
-            uint64_t slot = bn;
-            if constexpr (!DIRECT) {
-                const unsigned long long key = bn + 1;
-                slot = mix64(bn) & tmask;
-                // claimed by bank_seq_candidates; an empty slot cannot come first, it only ends the walk
-                for (unsigned long long cur = tkeys[slot]; cur != key && cur != 0ull; cur = tkeys[slot])
-                    slot = (slot + 1) & tmask;
+    [[maybe_unused]] unsigned long long fm = 0;   // LIST: a lane past n keeps 0 and still reaches the barriers
+    [[maybe_unused]] uint32_t fid = 0;
+    uint4 H = make_uint4(0u, 0u, 0u, 0u);
+    if (j < n) {
+        uint32_t isnew = 0;
+        unsigned long long cm = cand[j];
+        if (cm) {   // a key with a 0-probe passed the candidates' checks: its id is in range
+            H = digests[j];
+            const uint64_t id = ids[j];
+            if constexpr (LIST) fid = (uint32_t)id;
+            uint32_t* __restrict__ fb = g.bits + id * stride_words;
+            const uint64_t bit0 = id * stride_words * 32u;
+            while (cm) {
+                const uint32_t i = (uint32_t)__builtin_ctzll(cm);
+                cm &= cm - 1;
+                const uint64_t o = probe_offset(g, H.x, H.y, H.z, H.w, i);
+                const uint64_t bn = bit0 + o;
+                uint64_t slot = bn;
+                if constexpr (!DIRECT) {
+                    const unsigned long long key = bn + 1;
+                    slot = mix64(bn) & tmask;
+                    // claimed by bank_seq_candidates; an empty slot cannot come first, it only ends the walk
+                    for (unsigned long long cur = tkeys[slot]; cur != key && cur != 0ull; cur = tkeys[slot])
+                        slot = (slot + 1) & tmask;
+                }
+                isnew |= tvals[slot] == (uint32_t)j ? 1u : 0u;
+                const uint32_t bit = 1u << ((uint32_t)(o ^ 7u) & 31u);
+                [[maybe_unused]] const uint32_t old =
+                    __hip_atomic_fetch_or(fb + (o >> 5), bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if constexpr (LIST) fm |= (unsigned long long)((old & bit) ? 0u : 1u) << i;
             }
-            isnew |= tvals[slot] == (uint32_t)j ? 1u : 0u;
-            __hip_atomic_fetch_or(fb + (o >> 5), 1u << ((uint32_t)(o ^ 7u) & 31u), __ATOMIC_RELAXED,
-                                  __HIP_MEMORY_SCOPE_AGENT);
         }
+        if (out8) out8[j] = (uint8_t)isnew;
     }
-    if (out8) out8[j] = (uint8_t)isnew;
+    if constexpr (LIST) bank_list_tile(g, list, fm, fid, H.x, H.y, H.z, H.w);
 }
 
 // ---- cross query: one key against many filters ----------------------------------------------
@@ -909,6 +997,9 @@ struct bf_bank : BfHostCore {   // mutex, device, stream, error, stream order: b
     uint8_t* d_seq = nullptr;
     uint64_t seq_cap = 0;
     uint32_t seq_form = 0;             // bf_bank_set_seq_form: BF_BANK_SEQ_*
+    // bf_bank_insert_many_changes (host form): [count, 8 B | bits, 8 B an entry | ids, 4 B an entry]
+    uint8_t* d_chg = nullptr;
+    uint64_t chg_cap = 0;
 };
 
 namespace {
@@ -960,18 +1051,22 @@ int ensure_keys_io(bf_bank* b, uint64_t key_bytes, uint64_t n) {
     return BF_OK;
 }
 
+// list (insert only): the kernel also lists the bits it flipped.
 int launch_keys(bf_bank* b, int op, const uint8_t* d_keys, const uint64_t* d_off, const uint32_t* d_ids, uint64_t n,
-                uint8_t* d_out8, hipStream_t s) {
+                uint8_t* d_out8, hipStream_t s, const BankList<true>* list = nullptr) {
     if (n >= (1ull << 31) * (uint64_t)kBankTile) return bank_err(b, BF_EINVAL, "n too large for one launch");
     uint64_t bias = 0;
     const uint8_t* k16 = align_keys(d_keys, &bias);
     const dim3 grid((uint32_t)((n + kBankTile - 1) / kBankTile)), block(kBankTile);
-    if (op == BANK_INSERT)
+    if (op == BANK_INSERT && list)
+        hipLaunchKernelGGL((bank_keys_kernel<BANK_INSERT, true>), grid, block, 0, s, b->g, b->n_filters, b->stride / 4,
+                           k16, d_off, bias, d_ids, n, d_out8, b->d_status, *list);
+    else if (op == BANK_INSERT)
         hipLaunchKernelGGL(bank_keys_kernel<BANK_INSERT>, grid, block, 0, s, b->g, b->n_filters, b->stride / 4, k16,
-                           d_off, bias, d_ids, n, d_out8, b->d_status);
+                           d_off, bias, d_ids, n, d_out8, b->d_status, BankList<false>{});
     else
         hipLaunchKernelGGL(bank_keys_kernel<BANK_INCLUDE>, grid, block, 0, s, b->g, b->n_filters, b->stride / 4, k16,
-                           d_off, bias, d_ids, n, d_out8, b->d_status);
+                           d_off, bias, d_ids, n, d_out8, b->d_status, BankList<false>{});
     HIPCHK(b, hipGetLastError());
     return BF_OK;
 }
@@ -1112,8 +1207,9 @@ int ensure_seq_scratch(bf_bank* b, uint64_t need) {
 }
 
 // One chunk of at most bf_seq_chunk_keys(k) keys: clear, candidates, mark, in stream order.
+// list: the mark kernel also lists the bits it flipped.
 int launch_seq_chunk(bf_bank* b, bool direct, const uint8_t* d_keys, const uint64_t* d_off, const uint32_t* d_ids,
-                     uint64_t cn, uint8_t* d_out8, hipStream_t s) {
+                     uint64_t cn, uint8_t* d_out8, hipStream_t s, const BankList<true>* list = nullptr) {
     const BankSeqCarve c = seq_carve(b, direct, cn);
     if (c.tkeys) HIPCHK(b, hipMemsetAsync(c.tkeys, 0, c.slots * 8, s));
     HIPCHK(b, hipMemsetAsync(c.tvals, 0xFF, c.slots * 4, s));
@@ -1124,17 +1220,51 @@ int launch_seq_chunk(bf_bank* b, bool direct, const uint8_t* d_keys, const uint6
     if (direct) {
         hipLaunchKernelGGL(bank_seq_candidates_kernel<true>, grid, block, 0, s, b->g, b->n_filters, sw, k16, d_off, bias,
                            d_ids, cn, c.tkeys, c.tvals, 0, c.digests, c.cand, b->d_status);
-        hipLaunchKernelGGL(bank_seq_mark_kernel<true>, grid, block, 0, s, b->g, sw, d_ids, cn, c.tkeys, c.tvals, 0,
-                           c.digests, c.cand, d_out8);
+        if (list)
+            hipLaunchKernelGGL((bank_seq_mark_kernel<true, true>), grid, block, 0, s, b->g, sw, d_ids, cn, c.tkeys, c.tvals,
+                               0, c.digests, c.cand, d_out8, *list);
+        else
+            hipLaunchKernelGGL(bank_seq_mark_kernel<true>, grid, block, 0, s, b->g, sw, d_ids, cn, c.tkeys, c.tvals, 0,
+                               c.digests, c.cand, d_out8, BankList<false>{});
     } else {
         hipLaunchKernelGGL(bank_seq_candidates_kernel<false>, grid, block, 0, s, b->g, b->n_filters, sw, k16, d_off, bias,
                            d_ids, cn, c.tkeys, c.tvals, c.slots - 1, c.digests, c.cand, b->d_status);
-        hipLaunchKernelGGL(bank_seq_mark_kernel<false>, grid, block, 0, s, b->g, sw, d_ids, cn, c.tkeys, c.tvals,
-                           c.slots - 1, c.digests, c.cand, d_out8);
+        if (list)
+            hipLaunchKernelGGL((bank_seq_mark_kernel<false, true>), grid, block, 0, s, b->g, sw, d_ids, cn, c.tkeys,
+                               c.tvals, c.slots - 1, c.digests, c.cand, d_out8, *list);
+        else
+            hipLaunchKernelGGL(bank_seq_mark_kernel<false>, grid, block, 0, s, b->g, sw, d_ids, cn, c.tkeys, c.tvals,
+                               c.slots - 1, c.digests, c.cand, d_out8, BankList<false>{});
     }
     HIPCHK(b, hipGetLastError());
     return BF_OK;
 }
+
+// The sequential insert on device arrays, on an opened stream: the batch cut into chunks, every
+// chunk's list entries (list != NULL) added behind the ones before through the one counter.
+int seq_dev_chunks(bf_bank* b, const uint8_t* d_keys, const uint64_t* d_off, const uint32_t* d_ids, uint64_t n,
+                   uint8_t* d_out8, hipStream_t s, const BankList<true>* list) {
+    const uint64_t chunk = bf_seq_chunk_keys(b->k);
+    const bool direct = seq_direct(b, std::min<uint64_t>(n, chunk));
+    // synchronises only when the scratch has to grow
+    int rc = ensure_seq_scratch(b, seq_scratch_bytes(b, direct, std::min<uint64_t>(n, chunk)));
+    if (rc) return rc;
+    // offsets[0] need not be 0, so d_off + a is the offsets array of the keys from a on
+    for (uint64_t a = 0; a < n; a += chunk) {
+        const uint64_t cn = std::min<uint64_t>(n - a, chunk);
+        if ((rc = launch_seq_chunk(b, direct, d_keys, d_off + a, d_ids + a, cn, d_out8 ? d_out8 + a : nullptr, s, list)))
+            return rc;
+    }
+    return BF_OK;
+}
+
+// ---- the list of flipped bits: the host form's scratch ----------------------------------------
+
+// Up to this many bytes of [count | bits | ids] come back in one copy with the count; a longer list
+// is fetched after its count is known.  A per-key call (k entries) pays one round trip.
+constexpr uint64_t kChgOneCopy = 16u << 10;
+
+uint64_t chg_bytes(uint64_t entries) { return 8 + entries * 12; }
 
 // ids == NULL lists every filter in order; then count must be n_filters.
 int check_list(bf_bank* b, const uint32_t* ids, uint64_t count, bool host_ids) {
@@ -1378,7 +1508,7 @@ int bf_bank_destroy(bf_bank* b) {
         (void)hipStreamSynchronize(b->stream);
         if (b->order_valid) (void)hipEventSynchronize(b->order_ev);
         for (void* p : {(void*)b->g.bits, (void*)b->d_keys, (void*)b->d_out, (void*)b->d_off, (void*)b->d_ids,
-                        (void*)b->d_io, (void*)b->d_list, (void*)b->d_seq})
+                        (void*)b->d_io, (void*)b->d_list, (void*)b->d_seq, (void*)b->d_chg})
             if (p) (void)hipFree(p);
         if (b->order_ev) (void)hipEventDestroy(b->order_ev);
         if (b->h_status) (void)hipHostFree(b->h_status);
@@ -1509,19 +1639,111 @@ int bf_bank_insert_many_seq_dev(bf_bank* b, const uint8_t* d_key_bytes, const ui
     if (!d_key_bytes || !d_offsets || !d_filter_ids) return bank_err(b, BF_EINVAL, "NULL device pointer");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (int orc = cs.open(s)) return orc;
-    const uint64_t chunk = bf_seq_chunk_keys(b->k);
-    const bool direct = seq_direct(b, std::min<uint64_t>(n, chunk));
-    // synchronises only when the scratch has to grow
-    int rc = ensure_seq_scratch(b, seq_scratch_bytes(b, direct, std::min<uint64_t>(n, chunk)));
-    if (rc) return rc;
-    // offsets[0] need not be 0, so d_offsets + a is the offsets array of the keys from a on
-    for (uint64_t a = 0; a < n; a += chunk) {
-        const uint64_t cn = std::min<uint64_t>(n - a, chunk);
-        if ((rc = launch_seq_chunk(b, direct, d_key_bytes, d_offsets + a, d_filter_ids + a, cn,
-                                   d_per_key_new ? d_per_key_new + a : nullptr, s)))
-            return rc;
+    return seq_dev_chunks(b, d_key_bytes, d_offsets, d_filter_ids, n, d_per_key_new, s, nullptr);
+}
+
+int bf_bank_insert_many_changes(bf_bank* b, const uint8_t* key_bytes, const uint64_t* offsets,
+                                const uint32_t* filter_ids, uint64_t n, uint32_t seq, uint8_t* flags,
+                                uint32_t* out_ids, uint64_t* out_bits, uint64_t cap, uint64_t* count) {
+    if (!b || !count) return BF_EINVAL;
+    CallScope cs(b);
+    if (seq > 1) return bank_err(b, BF_EINVAL, "seq must be 0 or 1, got %u", seq);
+    if (cap && (!out_ids || !out_bits)) return bank_err(b, BF_EINVAL, "cap > 0 with a NULL out_ids / out_bits");
+    if (n == 0) {
+        *count = 0;
+        return BF_OK;
     }
+    int rc = check_batch(b, key_bytes, offsets, filter_ids, n);
+    if (rc) return rc;
+    if (int orc = cs.open(b->stream)) return orc;
+    // run_host's chunks; seq: bf_bank_insert_many_seq's form, chunk bound and scratch
+    const uint64_t seq_chunk = bf_seq_chunk_keys(b->k);
+    const uint64_t max_keys = seq ? std::min<uint64_t>(b->batch_keys, seq_chunk) : b->batch_keys;
+    const bool direct = seq && seq_direct(b, std::min<uint64_t>(n, seq_chunk));
+    if (seq && (rc = ensure_seq_scratch(b, seq_scratch_bytes(b, direct, std::min<uint64_t>(n, max_keys))))) return rc;
+    std::vector<uint64_t> rebased;
+    std::vector<uint8_t> back;
+    uint64_t a = 0, total = 0, written = 0;
+    while (a < n) {
+        uint64_t e = std::min<uint64_t>(n, a + max_keys);
+        if (offsets[e] - offsets[a] > b->batch_bytes) {
+            e = (uint64_t)(std::upper_bound(offsets + a, offsets + e + 1, offsets[a] + b->batch_bytes) - offsets) - 1;
+            if (e <= a) e = a + 1;
+        }
+        const uint64_t cn = e - a, nbytes = offsets[e] - offsets[a];
+        // the chunk lists into the bank's scratch: what the caller's arrays still hold, at most a
+        // probe per entry
+        uint64_t entries = cap - written;
+        if (entries / b->k >= cn) entries = cn * b->k;
+        if (entries > (UINT64_MAX - 8) / 12) return bank_err(b, BF_ENOMEM, "a list of %llu entries", (unsigned long long)entries);
+        if ((rc = ensure_keys_io(b, nbytes, cn))) return rc;
+        if ((rc = grow(b, (void**)&b->d_chg, &b->chg_cap, chg_bytes(entries)))) return rc;
+        unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(b->d_chg);
+        uint64_t* d_bits = reinterpret_cast<uint64_t*>(b->d_chg + 8);
+        uint32_t* d_lids = reinterpret_cast<uint32_t*>(b->d_chg + 8 + entries * 8);
+        const BankList<true> list{d_lids, d_bits, entries, d_cnt};
+        rebased.resize(cn + 1);
+        for (uint64_t j = 0; j <= cn; ++j) rebased[j] = offsets[a + j] - offsets[a];
+        if (nbytes) HIPCHK(b, hipMemcpyAsync(b->d_keys, key_bytes + offsets[a], nbytes, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(b, hipMemsetAsync(b->d_keys + nbytes, 0, 16, b->stream));
+        HIPCHK(b, hipMemcpyAsync(b->d_off, rebased.data(), (cn + 1) * 8, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(b, hipMemcpyAsync(b->d_ids, filter_ids + a, cn * 4, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(b, hipMemsetAsync(d_cnt, 0, 8, b->stream));
+        uint8_t* d_flags = flags ? b->d_out : nullptr;
+        if (seq) rc = launch_seq_chunk(b, direct, b->d_keys, b->d_off, b->d_ids, cn, d_flags, b->stream, &list);
+        else rc = launch_keys(b, BANK_INSERT, b->d_keys, b->d_off, b->d_ids, cn, d_flags, b->stream, &list);
+        if (rc) return rc;
+        if (flags) HIPCHK(b, hipMemcpyAsync(flags + a, b->d_out, cn, hipMemcpyDeviceToHost, b->stream));
+        unsigned long long flipped = 0;
+        const bool one_copy = chg_bytes(entries) <= kChgOneCopy;
+        if (one_copy) {
+            back.resize(chg_bytes(entries));
+            HIPCHK(b, hipMemcpyAsync(back.data(), b->d_chg, back.size(), hipMemcpyDeviceToHost, b->stream));
+        } else {
+            HIPCHK(b, hipMemcpyAsync(&flipped, d_cnt, 8, hipMemcpyDeviceToHost, b->stream));
+        }
+        HIPCHK(b, hipStreamSynchronize(b->stream));   // the staging buffers and `rebased` are free again
+        if (one_copy) memcpy(&flipped, back.data(), 8);
+        const uint64_t got = std::min<uint64_t>(flipped, entries);   // this chunk's entries behind the earlier ones
+        if (got && one_copy) {
+            memcpy(out_bits + written, back.data() + 8, got * 8);
+            memcpy(out_ids + written, back.data() + 8 + entries * 8, got * 4);
+        } else if (got) {
+            HIPCHK(b, hipMemcpyAsync(out_bits + written, d_bits, got * 8, hipMemcpyDeviceToHost, b->stream));
+            HIPCHK(b, hipMemcpyAsync(out_ids + written, d_lids, got * 4, hipMemcpyDeviceToHost, b->stream));
+            HIPCHK(b, hipStreamSynchronize(b->stream));
+        }
+        written += got;
+        total += flipped;
+        a = e;
+    }
+    *count = total;
+    if (total > cap)
+        return bank_err(b, BF_ERANGE, "the batch flipped %llu bits, the lists hold %llu (the insert is applied, the first "
+                                      "%llu entries are valid)",
+                        (unsigned long long)total, (unsigned long long)cap, (unsigned long long)cap);
     return BF_OK;
+}
+
+int bf_bank_insert_many_changes_dev(bf_bank* b, const uint8_t* d_key_bytes, const uint64_t* d_offsets,
+                                    const uint32_t* d_filter_ids, uint64_t n, uint32_t seq, uint8_t* d_flags,
+                                    uint32_t* d_out_ids, uint64_t* d_out_bits, uint64_t cap, uint64_t* d_count,
+                                    void* stream) {
+    if (!b) return BF_EINVAL;
+    CallScope cs(b);
+    if (seq > 1) return bank_err(b, BF_EINVAL, "seq must be 0 or 1, got %u", seq);
+    if (!d_count || (cap && (!d_out_ids || !d_out_bits)) || (n && (!d_key_bytes || !d_offsets || !d_filter_ids)))
+        return bank_err(b, BF_EINVAL, "NULL device pointer");
+    if ((reinterpret_cast<uintptr_t>(d_out_bits) & 7u) || (reinterpret_cast<uintptr_t>(d_count) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_out_ids) & 3u))
+        return bank_err(b, BF_EINVAL, "misaligned device pointer (d_out_bits and d_count: 8 bytes, d_out_ids: 4)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (int orc = cs.open(s)) return orc;
+    HIPCHK(b, hipMemsetAsync(d_count, 0, 8, s));   // the kernels of every chunk add to it
+    if (n == 0) return BF_OK;
+    const BankList<true> list{d_out_ids, d_out_bits, cap, reinterpret_cast<unsigned long long*>(d_count)};
+    if (seq) return seq_dev_chunks(b, d_key_bytes, d_offsets, d_filter_ids, n, d_flags, s, &list);
+    return launch_keys(b, BANK_INSERT, d_key_bytes, d_offsets, d_filter_ids, n, d_flags, s, &list);
 }
 
 int bf_bank_across_row_bytes(uint64_t count, uint64_t* bytes) {

@@ -47,6 +47,16 @@ flags: the keys grouped by id through 10^3 ``Filter`` handles' ``insert_many_dev
 flags of (a) and (c) and the bits of all of them are compared once outside the timed region.
 
     python tools/bench_bank.py --seq [--filters 1000,100000] [--runs 25] [--out profiles/bank_seq.json]
+
+--changes times what listing the flipped bits costs (bf_bank_insert_many_changes_dev, cap = n k)
+on the first workload: against bf_bank_insert_many_dev for seq = 0 and bf_bank_insert_many_seq_dev
+for seq = 1, the two alternating, a cleared bank before every run, median / min / max.  The list's
+length and distinctness are checked once outside the timed region.  Then the facade: one
+``bank[name].insert(key)`` of a new key into a half-full 10k @ 1 % key name with FakeRedis under
+``sync='write_through'`` and ``'write_through_bits'``: microseconds per call (host clock; the call
+ends in a device synchronise), and the bytes and SETBITs FakeRedis received per call.
+
+    python tools/bench_bank.py --changes [--filters 1000,100000] [--runs 25] [--out profiles/bank_changes.json]
 """
 import argparse
 import json
@@ -525,6 +535,81 @@ def run_combine(pkg, m, k, runs, warmup, only=None) -> list:
     return shapes
 
 
+# ---- --changes: what listing the flipped bits costs, on the device and at the facade -------------
+
+def run_changes(pkg, m, k, nf, n, buf, offs, runs, warmup) -> dict:
+    """run_bank's insert through bf_bank_insert_many_changes_dev (cap = n k) against the call
+    without a list, for both flag kinds; every insert starts from the cleared bank."""
+    ids = np.random.default_rng([0xBA2C, nf]).integers(0, nf, n).astype(np.uint32)
+    dk, do, di = to_dev(buf, offs, ids)
+    cap = n * k
+    flags = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    out_ids = torch.zeros(cap, dtype=torch.int32, device="cuda")
+    out_bits = torch.zeros(cap, dtype=torch.int64, device="cuda")
+    count = torch.zeros(1, dtype=torch.int64, device="cuda")
+    res = {"n_filters": nf, "cap": cap, "list_bytes": cap * 12}
+    args = (dk.data_ptr(), do.data_ptr(), di.data_ptr(), n)
+    with pkg.FilterBank(m, k, nf, device=0) as bank:
+        res["stride"], res["device_bytes"] = bank.stride, bank.device_bytes
+        clear = lambda: bank.clear_dev(stream=0)   # noqa: E731
+        for seq, name in ((0, "plain"), (1, "seq")):
+            without = (lambda: bank.insert_many_seq_dev(*args, flags.data_ptr(), stream=0)) if seq else \
+                (lambda: bank.insert_many_dev(*args, flags.data_ptr(), stream=0))
+            listing = lambda: bank.insert_many_changes_dev(   # noqa: E731
+                *args, d_count=count.data_ptr(), d_out_ids=out_ids.data_ptr(), d_out_bits=out_bits.data_ptr(), cap=cap,
+                seq=seq, d_flags=flags.data_ptr(), stream=0)
+            t_without, t_listing = timed_alternating([without, listing], [clear, clear], runs, warmup)
+            torch.cuda.synchronize()
+            bank.sync()
+            # the last timed call was the listing one, into the cleared bank: its list is every set bit, once
+            total = int(count.item())
+            assert total == int(bank.bitcount().sum()), "the list's length is not the bank's bit count"
+            named = out_ids[:total].to(torch.int64) * m + out_bits[:total]
+            assert int(torch.unique(named).numel()) == total, "a bit is listed twice"
+            assert 0 <= int(out_bits[:total].min()) and int(out_bits[:total].max()) < m
+            r = {"without_list": span(t_without), "with_list": span(t_listing), "flipped_bits": total}
+            r["ratio"] = round(r["with_list"]["ms"] / r["without_list"]["ms"], 3)
+            r["ranges_overlap"] = bool(t_listing[0] <= t_without[-1])
+            res[name] = r
+            print("%d filters, %s: %.3f ms [%.3f, %.3f] without a list, %.3f ms [%.3f, %.3f] with it (%d bits)" % (
+                nf, name, r["without_list"]["ms"], t_without[0], t_without[-1], r["with_list"]["ms"], t_listing[0],
+                t_listing[-1], total), file=sys.stderr, flush=True)
+    return res
+
+
+def run_changes_facade(pkg, calls: int) -> dict:
+    """One ``bank[name].insert(key)`` of a new key into a half-full 10k @ 1 % key name, FakeRedis
+    behind it, under the two write-through modes."""
+    names = ["tenant:%d" % i for i in range(5)]
+    fill = ["fill-%d" % i for i in range(FILL_PER_FILTER)]
+    res = {"calls": calls, "key_names": len(names), "fill_per_filter": FILL_PER_FILTER}
+    for mode in ("write_through", "write_through_bits"):
+        r = pkg.FakeRedis()
+        bank = pkg.BloomfilterBank(size=SIZE, error_rate=ERROR_RATE, key_names=names, redis=r, sync=mode)
+        for name in names:
+            bank.insert_many([name] * len(fill), fill)
+        view = bank[names[2]]
+        for i in range(20):
+            view.insert("warm-%d" % i)
+        r.calls.clear()
+        bytes0, us = r.bytes_in, []
+        for i in range(calls):
+            t0 = time.perf_counter()
+            view.insert("new-%d" % i)
+            us.append((time.perf_counter() - t0) * 1e6)
+        us.sort()
+        res[mode] = {"us_per_call": round(statistics.median(us), 1), "min_us": round(us[0], 1), "max_us": round(us[-1], 1),
+                     "bytes_in_per_call": round((r.bytes_in - bytes0) / calls, 1),
+                     "setbits_per_call": round(sum(1 for c in r.calls if c[0] == "SETBIT") / calls, 2),
+                     "setranges_per_call": round(sum(1 for c in r.calls if c[0] == "SETRANGE") / calls, 2),
+                     "string_bytes": len(r.get(names[2]))}
+        print("%s: %.1f us per insert, %.1f bytes and %.2f SETBITs per call" % (
+            mode, res[mode]["us_per_call"], res[mode]["bytes_in_per_call"], res[mode]["setbits_per_call"]),
+            file=sys.stderr, flush=True)
+        bank.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--filters", default="1000,100000")
@@ -540,6 +625,10 @@ def main():
     ap.add_argument("--seq", action="store_true",
                     help="time the insert with sequential flags against the plain insert and the handles "
                          "(profiles/bank_seq.json)")
+    ap.add_argument("--changes", action="store_true",
+                    help="time the insert that lists its flipped bits against the one that does not, and a per-key "
+                         "facade insert under the two write-through modes (profiles/bank_changes.json)")
+    ap.add_argument("--facade-calls", type=int, default=500, help="--changes: timed per-key inserts per sync mode")
     ap.add_argument("--only", choices=["small", "many", "big"], default=None,
                     help="--combine: the shapes of one bank only (10^3 filters, 10^4 filters, 5 x 120 MB)")
     args = ap.parse_args()
@@ -578,6 +667,18 @@ def main():
                "key_bytes": KEY_BYTES, "runs": args.runs, "warmup": args.warmup,
                "banks": {str(nf): run_seq(pkg, m, k, int(nf), n, buf, offs, args.runs, args.warmup)
                          for nf in args.filters.split(",")}}
+        line = json.dumps(doc)
+        print(line)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return
+    if args.changes:
+        doc = {"tool": "tools/bench_bank.py --changes", "device": torch.cuda.get_device_name(0), "m": m, "k": k, "keys": n,
+               "key_bytes": KEY_BYTES, "runs": args.runs, "warmup": args.warmup,
+               "banks": {str(nf): run_changes(pkg, m, k, int(nf), n, buf, offs, args.runs, args.warmup)
+                         for nf in args.filters.split(",")},
+               "facade": run_changes_facade(pkg, args.facade_calls)}
         line = json.dumps(doc)
         print(line)
         if args.out:
