@@ -265,6 +265,42 @@ int  bf_device_bits(bf_handle* h, void** d_bits, uint64_t* device_bytes);
  * The choice never changes results; BFHIP_INSERT_BINNED=0/1 forces it. */
 int  bf_insert_plan(const bf_handle* h, uint64_t n, uint32_t* binned, uint64_t* scratch_bytes);
 
+/* Which kernel variants a binned insert takes (no launch, read-only).  The binned pipeline
+ * picks its kernels from the shape of the call; every field below comes from the predicate
+ * the launch code itself branches on, so a test can assert the variant it is about.  A batch
+ * larger than one binned launch takes goes in `passes` sub-batches; everything else describes
+ * the first of them.  Libraries built with the A/B knobs (-DBFHIP_AB_KNOBS) describe the
+ * defaults: a knob's override of a variant is not reflected here. */
+typedef struct bf_plan_detail {
+    uint64_t passes;          /* sub-batches (launches) the batch is cut into */
+    uint64_t tiles;           /* front tiles of the sub-batch */
+    uint64_t scratch_bytes;   /* device scratch the sub-batch's plan needs */
+    uint32_t planned;         /* 1 if a binned plan exists for this shape; else all other fields are 0 */
+    uint32_t binned;          /* bf_insert_plan's *binned (bf_binned_plan_detail: = planned) */
+    uint32_t region_log2;     /* bits per region (LDS image): 2^18, 2^19 or 2^20 */
+    uint32_t regions;         /* regions covering the device bitset */
+    uint32_t superbins;       /* level-1 partitions (<= 256) */
+    uint32_t groups;          /* groups of front workgroups = level-2 windows per superbin */
+    uint32_t tiles_per_block; /* front tiles per front workgroup */
+    uint32_t front;           /* 0: two keys per lane (k <= 6), 1: 12 probe slots, 2: wide, 16 slots */
+    uint32_t scan;            /* window scan, 0: one workgroup, 1: hierarchical (three kernels) */
+    uint32_t density;         /* 2: >= 1 probe per 16-B vector (regions read first and written back
+                               * whole), 1: >= 1 per 128-B line (read first), 0: sparse */
+    uint32_t apply;           /* 0: one workgroup per region, 1: persistent pipelined kernel */
+    uint32_t apply_loads;     /* probe loads per lane and step of the per-region kernel at 2^19-bit
+                               * regions: 2 or 8; 0 for every other variant */
+} bf_plan_detail;
+/* Handle-free and host-only (works without a GPU): a bitset of device_bytes bytes (bf_info),
+ * k hashes, a batch of n keys, the preferred region size (18, 19 or 20; BFHIP_BIN_REGION_LOG2)
+ * and the device's compute units (0: the current device's, or 256 without one).  BF_OK with
+ * planned = 0 for a shape outside the binned path (k = 0, k > 16, n = 0, too many regions). */
+int  bf_binned_plan_detail(uint64_t device_bytes, uint32_t k, uint64_t n, uint32_t region_log2_pref,
+                           uint32_t compute_units, bf_plan_detail* out);
+/* The same for one bf_insert_many_dev call of n keys on this handle (its device bytes, k and
+ * region preference, compute_units = 0); binned is decided as in bf_insert_plan.  A
+ * multi-device handle answers for its first device. */
+int  bf_insert_plan_detail(const bf_handle* h, uint64_t n, bf_plan_detail* out);
+
 /* ---- incremental Redis sync.  With tracking on, every insert
  *      (direct, binned and sequential paths) marks the BF_DIRTY_BLOCK_BYTES blocks
  *      of the Redis string it may have changed; imports mark everything; bf_clear

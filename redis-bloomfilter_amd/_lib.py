@@ -61,6 +61,17 @@ class bf_config(ctypes.Structure):
                 ("devices", ctypes.c_int32 * BF_MAX_DEVICES)]
 
 
+class bf_plan_detail(ctypes.Structure):
+    _fields_ = [("passes", ctypes.c_uint64), ("tiles", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64),
+                ("planned", ctypes.c_uint32), ("binned", ctypes.c_uint32), ("region_log2", ctypes.c_uint32),
+                ("regions", ctypes.c_uint32), ("superbins", ctypes.c_uint32), ("groups", ctypes.c_uint32),
+                ("tiles_per_block", ctypes.c_uint32), ("front", ctypes.c_uint32), ("scan", ctypes.c_uint32),
+                ("density", ctypes.c_uint32), ("apply", ctypes.c_uint32), ("apply_loads", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -98,6 +109,8 @@ SIGNATURES = {
     "bf_insert_encode_region_sets_dev": (ctypes.c_int, [_vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _u64, _vp, _u64,
                                                         _vp]),
     "bf_insert_plan": (ctypes.c_int, [_vp, _u64, _u32p, _u64p]),
+    "bf_binned_plan_detail": (ctypes.c_int, [_u64, _u32, _u64, _u32, _u32, ctypes.POINTER(bf_plan_detail)]),
+    "bf_insert_plan_detail": (ctypes.c_int, [_vp, _u64, ctypes.POINTER(bf_plan_detail)]),
     "bf_track_dirty": (ctypes.c_int, [_vp, _u32]),
     "bf_dirty_ranges": (ctypes.c_int, [_vp, _u64p, _u32, _u32p, _u64p, _u32]),
     "bf_export_range": (ctypes.c_int, [_vp, _u64, _u64, _vp]),
@@ -295,6 +308,26 @@ def indexes(key: bytes, m: int, k: int) -> List[int]:
     out = np.zeros(max(int(k), 1), np.uint64)
     _check(load().bf_indexes(_ptr(buf), len(key), int(m), int(k), _ptr(out)))
     return [int(x) for x in out[: int(k)]]
+
+
+def device_bytes_for(m_bits: int, k: int) -> int:
+    """Bytes of the device bitset of a whole (unsharded) filter of m bits and k hashes, as
+    bf_info reports them: the reachable prefix min(m, k (2^32 - 1) + 1) in whole bytes, rounded
+    up to 256."""
+    bits = min(int(m_bits), int(k) * 0xFFFFFFFF + 1)
+    return -(-max((bits + 7) // 8, 1) // 256) * 256
+
+
+def binned_plan_detail(device_bytes: int, k: int, n: int, region_log2_pref: int = 19,
+                       compute_units: int = 0) -> dict:
+    """Which kernel variants a binned insert of n keys takes on a bitset of device_bytes bytes
+    (bf_binned_plan_detail): host-only, no handle, no GPU needed.  compute_units 0: the current
+    device's (256 without one).  The fields of bf_plan_detail as a dict of ints; "planned" is 0
+    for a shape outside the binned path."""
+    d = bf_plan_detail()
+    _check(load().bf_binned_plan_detail(int(device_bytes), int(k), int(n), int(region_log2_pref),
+                                        int(compute_units), ctypes.byref(d)))
+    return d.as_dict()
 
 
 def check_offsets(offsets: np.ndarray) -> None:
@@ -679,6 +712,13 @@ class Filter:
         b, sb = ctypes.c_uint32(), ctypes.c_uint64()
         _check(self._lib.bf_insert_plan(self.handle, int(n), ctypes.byref(b), ctypes.byref(sb)), self._h)
         return {"binned": bool(b.value), "scratch_bytes": int(sb.value)}
+
+    def insert_plan_detail(self, n: int) -> dict:
+        """Which kernel variants one insert_many_dev of n keys takes (bf_insert_plan_detail):
+        the fields of bf_plan_detail as a dict of ints."""
+        d = bf_plan_detail()
+        _check(self._lib.bf_insert_plan_detail(self.handle, int(n), ctypes.byref(d)), self._h)
+        return d.as_dict()
 
     def profile(self, enable: bool) -> None:
         """Per-kernel HIP-event timing of every keyed launch (bf_profile)."""

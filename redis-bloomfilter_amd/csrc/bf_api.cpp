@@ -2501,6 +2501,31 @@ int bf_insert_plan(const bf_handle* h, uint64_t n, uint32_t* binned, uint64_t* s
     return BF_OK;
 }
 
+int bf_binned_plan_detail(uint64_t device_bytes, uint32_t k, uint64_t n, uint32_t region_log2_pref,
+                          uint32_t compute_units, bf_plan_detail* out) {
+    if (!out) return BF_EINVAL;
+    *out = bf_plan_detail{};
+    // as launch_op cuts a batch: sub-batches of at most bf_binned_max_keys keys, the first described
+    const uint64_t sub = std::max<uint64_t>(1, bf_binned_max_keys(k, device_bytes, region_log2_pref));
+    BfBinPlan plan{};
+    if (!bf_binned_plan(device_bytes, std::min(n, sub), k, region_log2_pref, false, &plan)) return BF_OK;
+    out->planned = out->binned = 1;
+    out->passes = (n + sub - 1) / sub;
+    bf_binned_describe(plan, k, compute_units, out);
+    return BF_OK;
+}
+
+int bf_insert_plan_detail(const bf_handle* h, uint64_t n, bf_plan_detail* out) {
+    if (h && h->multi) return bfm_insert_plan_detail(h->multi, n, out);
+    if (!h) return BF_EINVAL;
+    const int rc = bf_binned_plan_detail(h->dev_bytes, h->k, n, h->bin_region_log2, 0, out);
+    if (rc != BF_OK) return rc;
+    uint32_t b = 0;
+    (void)bf_insert_plan(h, n, &b, nullptr);
+    out->binned = b;
+    return BF_OK;
+}
+
 }  // extern "C"
 
 // ---- statistics and filter-to-filter combines (bf_stats.hip) --------------------------------

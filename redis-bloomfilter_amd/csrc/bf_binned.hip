@@ -32,6 +32,7 @@
 // The insert result equals atomic OR (idempotent, commutative); the include?
 // answer is the AND of the key's k bits (ruby.rb:20-30) without the early exit.
 #include "bf_device.h"
+#include "bfhip.h"   // bf_plan_detail
 
 #include <algorithm>
 #include <cmath>
@@ -2205,6 +2206,50 @@ __global__ __launch_bounds__(1024) void chunk_unsort_kernel(BfChunkIn ci, uint32
     }
 }
 
+// ---- Which kernel variant a launch takes: one predicate per choice.  The launchers below
+// branch on these and bf_binned_describe reports them (bf_plan_detail), so a threshold lives
+// here once and a test can ask which side of it a shape is on.
+
+// Front pass, 0: two keys per lane (k <= kTwoKeys, tiles of 2 kTile keys), 1: one key per lane
+// in kSlots probe slots, 2: the wide front's kWideSlots slots.
+uint32_t front_form(uint32_t k) { return k <= kTwoKeys ? 0u : (k <= (uint32_t)kSlots ? 1u : 2u); }
+uint32_t front_tile_keys(uint32_t k) { return front_form(k) == 0 ? 2 * kTile : kTile; }
+
+// Window scan, 0: bin_group_scan_kernel's one workgroup, 1: the hierarchical three-kernel scan.
+uint32_t scan_form(uint32_t nsup, uint32_t ngroups) { return (uint64_t)nsup * ngroups <= kScanWindows ? 0u : 1u; }
+
+// Probe density over the regions, 2: at least one probe per 16-B vector on average (the region
+// is read before the probe pass and written back whole); 1: at least one per 128-B line (read
+// first, touched vectors written); 0: sparse.  Measured at 1B@1 % (13 probes / line, 2: 0.503
+// -> 0.492 ms) and 10B@0.01 % (4 / line, 1: 2.81 -> 2.65 ms; writing whole lines there: 2.81)
+uint32_t probe_density(uint64_t probes, uint32_t nbins, uint32_t region_log2) {
+    const uint64_t vecs = (uint64_t)nbins << (region_log2 - 7);
+    return probes >= vecs ? 2u : (probes >= vecs / 8 ? 1u : 0u);
+}
+
+// Apply form a density takes by default, 1: bin_apply_pipe_kernel, 0: bin_apply_kernel.  A batch
+// dense enough to rewrite whole regions (density 2, the north-star step: 0.52 -> 0.474 ms) takes
+// the pipelined form; a line-dense one (the 10B step, ~4 probes per line) keeps bin_apply (2.40
+// ms against 2.97 pipelined at one workgroup per CU: profiles/r03p_apply_pipe.jsonl; a
+// two-workgroup-per-CU form with only the run table prefetched measured 2.44: the 10B apply is
+// not bound by its dependent round trips).
+uint32_t apply_form_default(uint32_t density) { return density == 2 ? 1u : 0u; }
+
+// Whether the persistent pipelined apply runs, on a grid of `grid` workgroups (one per CU).  The
+// pipeline pays off over many regions per workgroup: a 150 MB shard (2288 regions, 9 per
+// workgroup) measured 0.206 pipelined against 0.164 ms (P = 8 owner insert).  2^18- and
+// 2^20-bit regions are not pipelined.
+bool apply_pipelined(uint32_t density, uint32_t form, uint32_t region_log2, uint32_t nbins, uint32_t grid) {
+    return density && form == 1 && region_log2 == 19 && grid && nbins >= 16 * grid;
+}
+
+// Level-2 loads per lane and gather step of the per-region kernels at 2^19-bit regions: a
+// region's probes over all 16 waves (2) when it has at most 16 x 64 x 4 of them on average,
+// else fewer waves with more loads in flight each (8).  10B@0.01 % (~2k probes per region):
+// 2.37 -> 2.25 ms; a P = 8 owner's insert (~44k per region): 0.16 ms at 8 against 0.23 at 2
+// (profiles/r04i_ab_apply_loads.jsonl)
+int region_loads(uint64_t probes, uint32_t nbins) { return probes <= (uint64_t)nbins * 4096u ? 2 : 8; }
+
 uint64_t align256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
 
 struct Carve {
@@ -2254,7 +2299,7 @@ Carve carve(const BfBinPlan& p, void* at0) {
 // hierarchical scan beyond.
 void launch_scan(const BfBinPlan& p, const Carve& c, hipStream_t s) {
     const uint32_t N = p.nsup * p.ngroups;
-    if (N <= kScanWindows) {
+    if (scan_form(p.nsup, p.ngroups) == 0) {
         hipLaunchKernelGGL(bin_group_scan_kernel, dim3(1), dim3(1024), 0, s, c.gsum, N, c.base, c.cb_base,
                            c.cb_window, c.cb_start, p.ngroups, (unsigned long long*)nullptr);
         return;
@@ -2293,17 +2338,18 @@ hipError_t launch_partition(const BfGeom& g, const BfBinPlan& p, const Carve& c,
                             const uint64_t* offsets, uint64_t bias, uint64_t n, uint8_t* out8, hipStream_t s,
                             BfMarks* mk, bool dig = false) {
     const uint32_t sup_log2 = p.region_log2 + p.rel_log2;
+    const bool wide = front_form(g.k) == 2;   // 16 probe slots per lane
     if (dig) {
         if (p.with_keys) return hipErrorInvalidValue;
         static const bool wide2 = [] {   // A/B: BFHIP_FRONT_WIDE2=0 takes one workgroup per CU
             const char* e = BF_AB_GETENV("BFHIP_FRONT_WIDE2");
             return !(e && e[0] == '0');
         }();
-        if (g.k > (uint32_t)kSlots && wide2)
+        if (wide && wide2)
             hipLaunchKernelGGL(bin_front_wide_dig_kernel, dim3(p.nblocks), dim3(kTile), 0, s, g, keys16, offsets, bias,
                                n, p.tile_keys, p.tiles_per_block, sup_log2, p.nsup, c.level1, c.level1_key, c.stab,
                                c.gcnt, out8);
-        else if (g.k > (uint32_t)kSlots)
+        else if (wide)
             hipLaunchKernelGGL((bin_front_wide_kernel<false, true>), dim3(p.nblocks), dim3(kTile), 0, s, g, keys16,
                                offsets, bias, n, p.tile_keys, p.tiles_per_block, sup_log2, p.nsup, c.level1,
                                c.level1_key, c.stab, c.gcnt, out8);
@@ -2314,7 +2360,7 @@ hipError_t launch_partition(const BfGeom& g, const BfBinPlan& p, const Carve& c,
         bf_mark(mk, s, "bin_front_digest");
         return launch_groups_mid(g, p, c, s, mk);
     }
-    if (g.k > (uint32_t)kSlots) {
+    if (wide) {
         if (p.with_keys)
             hipLaunchKernelGGL(bin_front_wide_kernel<true>, dim3(p.nblocks), dim3(kTile), 0, s, g, keys16, offsets,
                                bias, n, p.tile_keys, p.tiles_per_block, sup_log2, p.nsup, c.level1, c.level1_key,
@@ -2356,7 +2402,7 @@ uint64_t max_tiles(uint64_t bitset_bytes, uint32_t pref_region_log2) {
 
 uint64_t bf_binned_max_keys(uint32_t k, uint64_t bitset_bytes, uint32_t pref_region_log2) {
     if (k == 0) return 0;
-    const uint64_t tile_keys = k <= kTwoKeys ? 2 * kTile : kTile;
+    const uint64_t tile_keys = front_tile_keys(k);
     const uint64_t n = max_tiles(bitset_bytes, pref_region_log2) * tile_keys;
     return std::min<uint64_t>(n, ((1ull << 32) - 1) / k);
 }
@@ -2416,7 +2462,7 @@ uint32_t superbins(uint64_t bitset_bytes, uint32_t pref_region_log2) {
 bool bf_binned_plan(uint64_t bitset_bytes, uint64_t n, uint32_t k, uint32_t pref_region_log2, bool with_keys,
                     BfBinPlan* plan) {
     if (k == 0 || k > (uint32_t)kWideSlots || n == 0) return false;
-    return plan_common(bitset_bytes, n, k, k <= kTwoKeys ? 2 * kTile : kTile, pref_region_log2, with_keys, plan);
+    return plan_common(bitset_bytes, n, k, front_tile_keys(k), pref_region_log2, with_keys, plan);
 }
 
 bool bf_binned_plan_offsets(uint64_t bitset_bytes, uint64_t count, uint32_t pref_region_log2, BfBinPlan* plan,
@@ -2463,33 +2509,22 @@ uint32_t apply_pipe_grid() {
     return v;
 }
 
-// Dense apply form: 1 bin_apply_pipe_kernel, 0 bin_apply_kernel (BFHIP_APPLY_FORM, A/B).  By default a batch dense enough to rewrite whole regions (dense 2,
-// the north-star step: 0.52 -> 0.474 ms) takes the pipelined form; a line-dense one (the 10B
-// step, ~4 probes per line) keeps bin_apply (2.40 ms against 2.97 pipelined at one workgroup
-// per CU: profiles/r03p_apply_pipe.jsonl; a two-workgroup-per-CU form with only the run table
-// prefetched measured 2.44: the 10B apply is not bound by its dependent round trips).
+// Dense apply form: 1 bin_apply_pipe_kernel, 0 bin_apply_kernel: apply_form_default's choice
+// unless BFHIP_APPLY_FORM (A/B) forces one.
 uint32_t apply_form(uint32_t dense) {
     static const uint32_t v = [] {
         const char* e = BF_AB_GETENV("BFHIP_APPLY_FORM");
         return (e && e[0]) ? (uint32_t)std::strtoul(e, nullptr, 10) : 255u;
     }();
-    return v != 255u ? v : (dense == 2 ? 1u : 0u);
+    return v != 255u ? v : apply_form_default(dense);
 }
 
 hipError_t launch_apply(const BfGeom& g, const BfBinPlan& p, const Carve& c, uint64_t bitset_bytes,
                         uint32_t* any_flag, hipStream_t s, BfMarks* mk) {
     const uint64_t nwords = bitset_bytes / 4;
-    // dense = 2: at least one probe per 16-B vector on average (the region is read before the
-    // probe pass and written back whole); 1: at least one per 128-B line (read first, touched
-    // vectors written); 0: sparse.  Measured at 1B@1 % (13 probes / line, 2: 0.503 -> 0.492
-    // ms) and 10B@0.01 % (4 / line, 1: 2.81 -> 2.65 ms; writing whole lines there: 2.81)
-    const uint64_t vecs = (uint64_t)p.nbins << (p.region_log2 - 7);
-    const uint32_t dense = p.probes >= vecs ? 2u : (p.probes >= vecs / 8 ? 1u : 0u);
+    const uint32_t dense = probe_density(p.probes, p.nbins, p.region_log2);
     const uint32_t pg = apply_pipe_grid();
-    const uint32_t form = apply_form(dense);
-    // the pipeline pays off over many regions per workgroup: a 150 MB shard (2288 regions, 9
-    // per workgroup) measured 0.206 pipelined against 0.164 ms (P = 8 owner insert)
-    if (dense && pg && p.region_log2 == 19 && form == 1 && p.nbins >= 16 * pg) {   // 2^20-bit regions: not pipelined
+    if (apply_pipelined(dense, apply_form(dense), p.region_log2, p.nbins, pg)) {
         [[maybe_unused]] static const int pl = [] {
             const char* e = BF_AB_GETENV("BFHIP_APPLY_PIPE_LOADS");
             return e && *e && std::atoi(e) == 4 ? 4 : 8;
@@ -2509,16 +2544,13 @@ hipError_t launch_apply(const BfGeom& g, const BfBinPlan& p, const Carve& c, uin
                            g.bits, nwords, c.level2, c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups,
                            p.rel_log2, dense, any_flag, g.dirty, apply_store_fresh(), apply_xcd_group());
     else if (p.region_log2 == 19) {
-        // level-2 loads per lane and gather step: a region's probes over all 16 waves (2) when
-        // it has at most 16 x 64 x 4 of them, else fewer waves with more loads in flight each
-        // (8).  10B@0.01 % (~2k probes per region): 2.37 -> 2.25 ms; a P = 8 owner's insert
-        // (~44k per region): 0.16 ms at 8 against 0.23 at 2 (profiles/r04i_ab_apply_loads.jsonl)
+        // level-2 loads per lane and gather step (region_loads; BFHIP_APPLY_LOADS forces, A/B)
         static const int forced = [] {
             const char* e = BF_AB_GETENV("BFHIP_APPLY_LOADS");
             const int v = e && *e ? std::atoi(e) : 0;
             return v == 1 || v == 2 || v == 4 || v == 8 ? v : 0;
         }();
-        const int loads = forced ? forced : (p.probes <= (uint64_t)p.nbins * 4096u ? 2 : 8);
+        const int loads = forced ? forced : region_loads(p.probes, p.nbins);
 #define BF_APPLY19(LD)                                                                                          \
     hipLaunchKernelGGL((bin_apply_kernel<19, kApplyLanes, LD>), dim3(p.nbins), dim3(kApplyLanes), 0, s, g.bits, \
                        nwords, c.level2, c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups, p.rel_log2, dense, \
@@ -2540,6 +2572,24 @@ hipError_t launch_apply(const BfGeom& g, const BfBinPlan& p, const Carve& c, uin
 }
 
 }  // namespace
+
+// The choices launch_partition, launch_scan and launch_apply make for plan p, from the
+// predicates they branch on (the A/B overrides of an -DBFHIP_AB_KNOBS build are not described).
+void bf_binned_describe(const BfBinPlan& p, uint32_t k, uint32_t compute_units, bf_plan_detail* out) {
+    out->tiles = p.ntiles;
+    out->scratch_bytes = p.scratch_bytes;
+    out->region_log2 = p.region_log2;
+    out->regions = p.nbins;
+    out->superbins = p.nsup;
+    out->groups = p.ngroups;
+    out->tiles_per_block = p.tiles_per_block;
+    out->front = front_form(k);
+    out->scan = scan_form(p.nsup, p.ngroups);
+    out->density = probe_density(p.probes, p.nbins, p.region_log2);
+    const uint32_t grid = compute_units ? compute_units : apply_pipe_grid();
+    out->apply = apply_pipelined(out->density, apply_form_default(out->density), p.region_log2, p.nbins, grid) ? 1u : 0u;
+    out->apply_loads = (!out->apply && p.region_log2 == 19) ? (uint32_t)region_loads(p.probes, p.nbins) : 0u;
+}
 
 hipError_t bf_launch_insert_binned(const BfGeom& g, const BfBinPlan& p, uint64_t bitset_bytes,
                                    const uint8_t* keys16, const uint64_t* offsets, uint64_t bias, uint64_t n,
@@ -2696,7 +2746,7 @@ bool bf_route_plan(uint64_t n, uint32_t k, uint32_t shards, bool wide, bool with
     if (p.ntiles > (uint64_t)kMaxFrontBlocks * p.tiles_per_block) return false;
     p.nblocks = (uint32_t)((p.ntiles + p.tiles_per_block - 1) / p.tiles_per_block);
     p.ngroups = (p.nblocks + kGroupBlocks - 1) / kGroupBlocks;
-    if ((uint64_t)p.nsup * p.ngroups > kScanWindows) return false;   // one-workgroup scan (per-owner totals)
+    if (scan_form(p.nsup, p.ngroups) != 0) return false;   // one-workgroup scan (per-owner totals)
     p.probes = probes;
     p.max_chunks = (probes + kBlockProbes - 1) / kBlockProbes + (uint64_t)p.nsup * p.ngroups;
     p.scratch_bytes = route_carve(p, wide, with_slot, nullptr).bytes;
@@ -2906,9 +2956,8 @@ hipError_t bf_launch_shard_insert_test_chunks_packed(const BfGeom& g, const BfBi
     const uint64_t nwords = bitset_bytes / 4;
     const BfL2 li{ci_.level2, ci_.cb_base, ci_.cb_start, ci_.tabs, pi.max_chunks, pi.ngroups};
     const BfL2 lt{ct.level2, ct.cb_base, ct.cb_start, ct.tabs, pt.max_chunks, pt.ngroups};
-    const uint64_t vecs = (uint64_t)pi.nbins << (pi.region_log2 - 7);
-    const uint32_t dense = pi.probes >= vecs ? 2u : (pi.probes >= vecs / 8 ? 1u : 0u);
-    const int iloads = pi.probes <= (uint64_t)pi.nbins * 4096u ? 2 : 8;   // as launch_apply
+    const uint32_t dense = probe_density(pi.probes, pi.nbins, pi.region_log2);
+    const int iloads = region_loads(pi.probes, pi.nbins);   // as launch_apply
 #define BF_APPLY_TEST(RL, LANES, LD, SD)                                                                          \
     hipLaunchKernelGGL((bin_apply_test_kernel<RL, LANES, LD, SD>), dim3(pi.nbins), dim3(LANES), 0, s, g.bits, nwords, \
                        li, lt, pi.rel_log2, dense, any_flag, g.dirty, apply_store_fresh(), ct.ans2, side)
@@ -3980,7 +4029,7 @@ hipError_t bf_launch_encode_sets(const BfGeom& g, const BfBinPlan& p, uint64_t b
         const int v = e && *e ? std::atoi(e) : 0;
         return v == 8 || v == 4 || v == 2 || v == 1 ? v : 0;
     }();
-    const int loads = forced ? forced : (n * g.k <= (uint64_t)p.nbins * 4096u ? 2 : 8);
+    const int loads = forced ? forced : region_loads(n * g.k, p.nbins);
     uint32_t enc_grid = persistent_grid;
 #ifdef BFHIP_AB_KNOBS
     if (const char* e = BF_AB_GETENV("BFHIP_SETS_ENC_GRID")) enc_grid = (uint32_t)std::strtoul(e, nullptr, 10);   // (A/B)
@@ -4027,8 +4076,7 @@ hipError_t bf_launch_insert_sets(const BfGeom& g, uint64_t bitset_bytes, uint32_
                                  uint32_t* any_flag, uint32_t* status, hipStream_t s, BfMarks* mk) {
     if (nsrc == 0) return hipSuccess;
     const uint64_t nwords = bitset_bytes / 4;
-    const uint64_t vecs = (uint64_t)nbins << (region_log2 - 7);
-    const uint32_t dense = probes_hint >= vecs ? 2u : (probes_hint >= vecs / 8 ? 1u : 0u);
+    const uint32_t dense = probe_density(probes_hint, nbins, region_log2);
     // low-bit stage: 1 (default) 15 KB at 2^19-bit regions (two workgroups per CU), 7.5 KB at
     // 2^18; 0: none (A/B; a 48-KB stage at one workgroup per CU measured 7.07 against 4.72 ms
     // at 10B, profiles/r04g_ab_sets_stage.jsonl)
@@ -4050,7 +4098,7 @@ hipError_t bf_launch_insert_sets(const BfGeom& g, uint64_t bitset_bytes, uint32_
         const char* e = BF_AB_GETENV("BFHIP_SETS_PIPE");
         return e && e[0] == '1';
     }();
-    const bool pipe = pipe_on && dense && region_log2 == 19 && pg && nbins >= 16 * pg;
+    const bool pipe = pipe_on && apply_pipelined(dense, 1u, region_log2, nbins, pg);
 #endif
     for (uint32_t s0 = 0; s0 < nsrc; s0 += kMaxSetSrc) {
         const uint32_t ns = std::min<uint32_t>(kMaxSetSrc, nsrc - s0);
@@ -4111,10 +4159,9 @@ hipError_t bf_launch_insert_encode_sets(const BfGeom& g, const BfBinPlan& p, uin
     hipLaunchKernelGGL(sets_size_kernel, dim3(p.nsup), dim3(1024), 0, s, c.tabs, c.cb_base, p.max_chunks, p.ngroups,
                        p.rel_log2, p.nbins, 1u << p.region_log2, next_out, c.stot);
     hipLaunchKernelGGL(sets_place_kernel, dim3(1), dim3(1024), 0, s, next_out, c.stot, p.nsup, p.region_log2, p.nbins);
-    const int loads = n_next * g.k <= (uint64_t)p.nbins * 4096u ? 2 : 8;   // as bf_launch_encode_sets
+    const int loads = region_loads(n_next * g.k, p.nbins);   // as bf_launch_encode_sets
     const uint64_t nwords = bitset_bytes / 4;
-    const uint64_t vecs = (uint64_t)nbins << (region_log2 - 7);
-    const uint32_t dense = probes_hint >= vecs ? 2u : (probes_hint >= vecs / 8 ? 1u : 0u);
+    const uint32_t dense = probe_density(probes_hint, nbins, region_log2);
     const uint32_t xg = 2u;   // as bf_launch_insert_sets
 #define BF_SETS_APPLY_ENCODE(RL, LN, ST, LD)                                                                     \
     hipLaunchKernelGGL((sets_apply_encode_kernel<RL, LN, ST, LD>), dim3(nbins), dim3(LN), 0, s, g.bits, nwords, sets, \

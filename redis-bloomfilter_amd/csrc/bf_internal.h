@@ -197,6 +197,12 @@ uint64_t bf_binned_max_keys(uint32_t k, uint64_t bitset_bytes, uint32_t pref_reg
 // bf_binned_max_keys keys, or a bitset beyond 65536 regions of 2^20 bits).
 bool bf_binned_plan(uint64_t bitset_bytes, uint64_t n, uint32_t k, uint32_t pref_region_log2, bool with_keys,
                     BfBinPlan* plan);
+// The kernel variants a launch of plan p (k probes per key) takes, into the shape fields of
+// *out (bf_plan_detail of bfhip.h; planned, binned and passes are the caller's): filled from the
+// predicates launch_partition, launch_scan and launch_apply branch on.  compute_units 0: the
+// persistent apply's own grid (the current device's compute units, 256 without a device).
+struct bf_plan_detail;
+void bf_binned_describe(const BfBinPlan& p, uint32_t k, uint32_t compute_units, bf_plan_detail* out);
 hipError_t bf_launch_insert_binned(const BfGeom& g, const BfBinPlan& p, uint64_t bitset_bytes,
                                    const uint8_t* keys16, const uint64_t* offsets, uint64_t bias, uint64_t n,
                                    void* scratch, uint32_t* any_flag, hipStream_t s, BfMarks* marks = nullptr);

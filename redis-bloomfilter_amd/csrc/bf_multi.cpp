@@ -562,6 +562,10 @@ int bfm_insert_plan(const BfMulti* mh, uint64_t n, uint32_t* binned, uint64_t* s
     return bf_insert_plan(mh->sub[0], n, binned, scratch_bytes);
 }
 
+int bfm_insert_plan_detail(const BfMulti* mh, uint64_t n, bf_plan_detail* out) {
+    return bf_insert_plan_detail(mh->sub[0], n, out);
+}
+
 // ---- Redis string -----------------------------------------------------------------------
 
 int bfm_export_redis(BfMulti* mh, uint8_t* buf, uint64_t cap, uint64_t* len_out) {

@@ -32,6 +32,7 @@ int bfm_export_range(BfMulti* mh, uint64_t offset, uint64_t len, uint8_t* buf);
 // replicated: device 0's count; partitioned: the shards' sum, whole string only
 int bfm_bitcount(BfMulti* mh, uint64_t byte_start, uint64_t byte_len, uint64_t* set_bits);
 int bfm_insert_plan(const BfMulti* mh, uint64_t n, uint32_t* binned, uint64_t* scratch_bytes);
+int bfm_insert_plan_detail(const BfMulti* mh, uint64_t n, bf_plan_detail* out);   // the first device's
 int bfm_fail(BfMulti* mh, int code, const char* msg);
 
 // bf_api.cpp internals, valid on shard handles too (offsets in the handle's local bytes)

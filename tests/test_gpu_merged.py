@@ -25,6 +25,10 @@ def test_merged_insert_one_pass_equals_direct(pkg, monkeypatch):
     assert plan["binned"]
     # one pass: the scratch holds all n*k probes (two 4-B level arrays) at once
     assert plan["scratch_bytes"] >= 2 * 4 * n * k
+    # the variants this shape is here for: 436,368,101 probes over 436,207,616 vectors (density 2,
+    # the pipelined apply) and 208 superbins x 33 groups > 4096 windows (the hierarchical scan)
+    detail = fb.insert_plan_detail(n)
+    assert (detail["apply"], detail["scan"], detail["density"]) == (1, 1, 2), detail
     fb.profile(True)
     fb.profile_read(reset=True)
     fb.insert_many_dev(kb.data_ptr(), ko.data_ptr(), n, d_any_new=flags[0:1].data_ptr())
@@ -44,8 +48,12 @@ def test_merged_insert_one_pass_equals_direct(pkg, monkeypatch):
     b = D.device_bytes_view(fd)
     assert bool(torch.equal(a, b))
     assert flags.tolist() == [1, 1]
-    out = torch.empty(n, dtype=torch.uint8, device="cuda")
+    # zeroed, and read only after the handle's own (non-blocking) stream has finished: with
+    # torch.empty and no synchronize this read raced the kernel and saw whatever the block held
+    out = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
     fb.include_many_dev(kb.data_ptr(), ko.data_ptr(), n, out.data_ptr())
+    torch.cuda.synchronize()
     assert bool(out.all())
     fb.close()
     fd.close()

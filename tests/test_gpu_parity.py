@@ -301,8 +301,10 @@ def test_device_api_torch(pkg, oracle):
                                    (2**32 + 17, 7, 100_000), (95851, 6, 1_500_000)])
 def test_binned_insert_matches_oracle(pkg, oracle, monkeypatch, mode, m, k, n):
     """BFHIP_INSERT_BINNED / BFHIP_INCLUDE_BINNED = 1 force the binned (front/mid/apply|test)
-    insert and include?; 0 the direct kernels.  1.5M keys into one region: a superbin of more
-    than one run-table pass (> 1024 chunk blocks) and a region of many probe steps."""
+    insert and include?; 0 the direct kernels.  1.5M keys into one region: a region of many
+    probe steps.  (The host-pointer call cuts the batch into chunks of 2^20 keys, 768 chunk
+    blocks each, so no launch here exceeds one run-table pass of 1024 blocks; the one-launch
+    form of this shape is tests/test_gpu_binned_dense.py.)"""
     monkeypatch.setenv("BFHIP_INSERT_BINNED", mode)
     monkeypatch.setenv("BFHIP_INCLUDE_BINNED", mode)
     rng = np.random.default_rng(RNG_SEED + 7)
