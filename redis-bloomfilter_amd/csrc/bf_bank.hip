@@ -33,6 +33,13 @@
 //                       64 pairs per workgroup staged through LDS, the stride split over grid z
 //                       where the tiles are few.  bank_overlap_few_kernel streams at most 4 x 4
 //                       pairs of long filters without a tile.
+//
+// Host side: every host-pointer keyed call (insert, include?, the sequential and the listing
+// insert, the cross query) walks its batch with the same two steps: chunk_end cuts at the call's
+// key bound and at batch_bytes (a longer key goes alone), stage_chunk copies the chunk's keys,
+// offsets (from 0) and ids to the device.  The caller's loop launches, queues its copy-back and
+// synchronises.  seq_plan is the one place that decides a sequential call's table form, chunk
+// bound and scratch bytes, for bf_bank_seq_plan, the host forms and the _dev forms alike.
 #include "bfhip.h"
 #include "bf_device.h"
 #include "bf_host.h"
@@ -1058,36 +1065,86 @@ int launch_keys(bf_bank* b, int op, const uint8_t* d_keys, const uint64_t* d_off
     uint64_t bias = 0;
     const uint8_t* k16 = align_keys(d_keys, &bias);
     const dim3 grid((uint32_t)((n + kBankTile - 1) / kBankTile)), block(kBankTile);
-    if (op == BANK_INSERT && list)
-        hipLaunchKernelGGL((bank_keys_kernel<BANK_INSERT, true>), grid, block, 0, s, b->g, b->n_filters, b->stride / 4,
-                           k16, d_off, bias, d_ids, n, d_out8, b->d_status, *list);
-    else if (op == BANK_INSERT)
-        hipLaunchKernelGGL(bank_keys_kernel<BANK_INSERT>, grid, block, 0, s, b->g, b->n_filters, b->stride / 4, k16,
-                           d_off, bias, d_ids, n, d_out8, b->d_status, BankList<false>{});
-    else
-        hipLaunchKernelGGL(bank_keys_kernel<BANK_INCLUDE>, grid, block, 0, s, b->g, b->n_filters, b->stride / 4, k16,
-                           d_off, bias, d_ids, n, d_out8, b->d_status, BankList<false>{});
+#define BF_KEYS_LAUNCH(OP, LIST, list_arg)                                                                              \
+    hipLaunchKernelGGL((bank_keys_kernel<OP, LIST>), grid, block, 0, s, b->g, b->n_filters, b->stride / 4, k16, d_off, \
+                       bias, d_ids, n, d_out8, b->d_status, list_arg)
+    if (op == BANK_INSERT && list) BF_KEYS_LAUNCH(BANK_INSERT, true, *list);
+    else if (op == BANK_INSERT) BF_KEYS_LAUNCH(BANK_INSERT, false, BankList<false>{});
+    else BF_KEYS_LAUNCH(BANK_INCLUDE, false, BankList<false>{});
+#undef BF_KEYS_LAUNCH
     HIPCHK(b, hipGetLastError());
     return BF_OK;
 }
 
-// The host forms' refusals (nothing is launched): bf_check_offsets' rule and every id in range.
-int check_batch(bf_bank* b, const uint8_t* keys, const uint64_t* offsets, const uint32_t* ids, uint64_t n) {
-    if (!offsets || !ids || (!keys && offsets[n] != offsets[0])) return bank_err(b, BF_EINVAL, "NULL keys / offsets / filter_ids");
+// Every id of a host list below n_filters; `what` names the list in the refusal.
+int check_ids(bf_bank* b, const char* what, const uint32_t* ids, uint64_t count) {
+    for (uint64_t i = 0; i < count; ++i)
+        if ((uint64_t)ids[i] >= b->n_filters)
+            return bank_err(b, BF_EINVAL, "%s[%llu] = %u is not below n_filters = %llu", what, (unsigned long long)i, ids[i],
+                            (unsigned long long)b->n_filters);
+    return BF_OK;
+}
+
+// A _dev call's alignment refusal: the addresses (addr) that must be multiples of 8 ORed together,
+// and those of 4; `rule` spells the pointers out.
+uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
+int check_aligned(bf_bank* b, uintptr_t by8, uintptr_t by4, const char* rule) {
+    if ((by8 & 7u) || (by4 & 3u)) return bank_err(b, BF_EINVAL, "misaligned device pointer (%s)", rule);
+    return BF_OK;
+}
+
+// Key by key, lowest first: bf_check_offsets' rule, then (ids != NULL) the key's filter id in range.
+int check_keys(bf_bank* b, const uint64_t* offsets, const uint32_t* ids, uint64_t n) {
     const uint64_t lo = offsets[0], hi = offsets[n];
     for (uint64_t j = 0; j < n; ++j) {
         if (!key_ok(lo, offsets[j], offsets[j + 1], hi, nullptr))
             return bank_err(b, BF_EINVAL, "key %llu: offsets must be non-decreasing and every key below 2 GiB",
                             (unsigned long long)j);
-        if ((uint64_t)ids[j] >= b->n_filters)
+        if (ids && (uint64_t)ids[j] >= b->n_filters)
             return bank_err(b, BF_EINVAL, "key %llu: filter id %u is not below n_filters = %llu", (unsigned long long)j,
                             ids[j], (unsigned long long)b->n_filters);
     }
     return BF_OK;
 }
 
-// Host-pointer insert / include?: chunks of at most batch_keys keys and batch_bytes key bytes
-// (a longer key goes alone) staged on the bank's stream.
+// The host forms' refusals (nothing is launched).
+int check_batch(bf_bank* b, const uint8_t* keys, const uint64_t* offsets, const uint32_t* ids, uint64_t n) {
+    if (!offsets || !ids || (!keys && offsets[n] != offsets[0])) return bank_err(b, BF_EINVAL, "NULL keys / offsets / filter_ids");
+    return check_keys(b, offsets, ids, n);
+}
+
+// ---- the chunks of the host-pointer keyed calls -----------------------------------------------
+
+// Where the chunk that begins at key a ends: at most max_keys keys (the caller's bound) and, where
+// their bytes exceed batch_bytes, the longest run within it, at least one key (a longer key goes alone).
+uint64_t chunk_end(const bf_bank* b, const uint64_t* offsets, uint64_t n, uint64_t a, uint64_t max_keys) {
+    uint64_t e = std::min<uint64_t>(n, a + max_keys);
+    if (offsets[e] - offsets[a] > b->batch_bytes) {
+        e = (uint64_t)(std::upper_bound(offsets + a, offsets + e + 1, offsets[a] + b->batch_bytes) - offsets) - 1;
+        if (e <= a) e = a + 1;
+    }
+    return e;
+}
+
+// The keys [a, e) staged on the bank's stream: their bytes at d_keys with 16 zero bytes behind,
+// their offsets rebased to 0 at d_off (offsets[0] need not be 0), their ids at d_ids (ids == NULL:
+// a call without per-key ids).  The staging buffers and the caller's `rebased` are in use until
+// the caller has synchronised the stream.
+int stage_chunk(bf_bank* b, const uint8_t* keys, const uint64_t* offsets, const uint32_t* ids, uint64_t a, uint64_t e,
+                std::vector<uint64_t>& rebased) {
+    const uint64_t cn = e - a, nbytes = offsets[e] - offsets[a];
+    int rc = ensure_keys_io(b, nbytes, cn);
+    if (rc) return rc;
+    rebased.resize(cn + 1);
+    for (uint64_t j = 0; j <= cn; ++j) rebased[j] = offsets[a + j] - offsets[a];
+    if (nbytes) HIPCHK(b, hipMemcpyAsync(b->d_keys, keys + offsets[a], nbytes, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(b, hipMemsetAsync(b->d_keys + nbytes, 0, 16, b->stream));
+    HIPCHK(b, hipMemcpyAsync(b->d_off, rebased.data(), (cn + 1) * 8, hipMemcpyHostToDevice, b->stream));
+    if (ids) HIPCHK(b, hipMemcpyAsync(b->d_ids, ids + a, cn * 4, hipMemcpyHostToDevice, b->stream));
+    return BF_OK;
+}
+
+// Host-pointer insert / include?: chunks of at most batch_keys keys.
 int run_host(bf_bank* b, int op, const uint8_t* keys, const uint64_t* offsets, const uint32_t* ids, uint64_t n,
              uint8_t* out) {
     if (!b) return BF_EINVAL;
@@ -1097,26 +1154,13 @@ int run_host(bf_bank* b, int op, const uint8_t* keys, const uint64_t* offsets, c
     int rc = check_batch(b, keys, offsets, ids, n);
     if (rc) return rc;
     if (int orc = cs.open(b->stream)) return orc;
-    std::vector<uint64_t> rebased;
-    uint64_t a = 0;
-    while (a < n) {
-        uint64_t e = std::min<uint64_t>(n, a + b->batch_keys);
-        if (offsets[e] - offsets[a] > b->batch_bytes) {   // the longest run of keys within batch_bytes, at least one
-            e = (uint64_t)(std::upper_bound(offsets + a, offsets + e + 1, offsets[a] + b->batch_bytes) - offsets) - 1;
-            if (e <= a) e = a + 1;
-        }
-        const uint64_t cn = e - a, nbytes = offsets[e] - offsets[a];
-        if ((rc = ensure_keys_io(b, nbytes, cn))) return rc;
-        rebased.resize(cn + 1);
-        for (uint64_t j = 0; j <= cn; ++j) rebased[j] = offsets[a + j] - offsets[a];
-        if (nbytes) HIPCHK(b, hipMemcpyAsync(b->d_keys, keys + offsets[a], nbytes, hipMemcpyHostToDevice, b->stream));
-        HIPCHK(b, hipMemsetAsync(b->d_keys + nbytes, 0, 16, b->stream));
-        HIPCHK(b, hipMemcpyAsync(b->d_off, rebased.data(), (cn + 1) * 8, hipMemcpyHostToDevice, b->stream));
-        HIPCHK(b, hipMemcpyAsync(b->d_ids, ids + a, cn * 4, hipMemcpyHostToDevice, b->stream));
-        if ((rc = launch_keys(b, op, b->d_keys, b->d_off, b->d_ids, cn, out ? b->d_out : nullptr, b->stream))) return rc;
-        if (out) HIPCHK(b, hipMemcpyAsync(out + a, b->d_out, cn, hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(b, hipStreamSynchronize(b->stream));   // the staging buffers and `rebased` are free again
-        a = e;
+    std::vector<uint64_t> h_off;   // stage_chunk's, read by its copy until the synchronise
+    for (uint64_t a = 0, e; a < n; a = e) {
+        e = chunk_end(b, offsets, n, a, b->batch_keys);
+        if ((rc = stage_chunk(b, keys, offsets, ids, a, e, h_off))) return rc;
+        if ((rc = launch_keys(b, op, b->d_keys, b->d_off, b->d_ids, e - a, out ? b->d_out : nullptr, b->stream))) return rc;
+        if (out) HIPCHK(b, hipMemcpyAsync(out + a, b->d_out, e - a, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(b, hipStreamSynchronize(b->stream));   // the staging buffers are free again
     }
     return BF_OK;
 }
@@ -1173,6 +1217,21 @@ uint64_t seq_scratch_bytes(const bf_bank* b, bool direct, uint64_t cn) {
     return seq_table_bytes(b, direct, cn) + align256(cn * 16) + align256(cn * 8);
 }
 
+// How a sequential call of n keys runs (bf_bank_seq_plan reports it): the table's form, the keys
+// of its largest chunk and the scratch that chunk needs.  batch_keys is the caller's own bound on
+// a chunk (UINT64_MAX: none, the _dev forms).  The form is the call's, from min(n,
+// bf_seq_chunk_keys(k)) whatever batch_keys is; the scratch is sized for the chunks launched.
+struct BankSeqPlan {
+    bool direct;
+    uint64_t chunk, scratch;
+};
+
+BankSeqPlan seq_plan(const bf_bank* b, uint64_t n, uint64_t batch_keys) {
+    const uint64_t by_width = bf_seq_chunk_keys(b->k), chunk = std::min<uint64_t>(n, std::min<uint64_t>(batch_keys, by_width));
+    const bool direct = seq_direct(b, std::min<uint64_t>(n, by_width));
+    return {direct, chunk, chunk ? seq_scratch_bytes(b, direct, chunk) : 0};
+}
+
 BankSeqCarve seq_carve(const bf_bank* b, bool direct, uint64_t cn) {
     BankSeqCarve c{};
     uint8_t* at = b->d_seq;
@@ -1216,26 +1275,21 @@ int launch_seq_chunk(bf_bank* b, bool direct, const uint8_t* d_keys, const uint6
     uint64_t bias = 0;
     const uint8_t* k16 = align_keys(d_keys, &bias);
     const dim3 grid((uint32_t)((cn + kBankTile - 1) / kBankTile)), block(kBankTile);
-    const uint64_t sw = b->stride / 4;
-    if (direct) {
-        hipLaunchKernelGGL(bank_seq_candidates_kernel<true>, grid, block, 0, s, b->g, b->n_filters, sw, k16, d_off, bias,
-                           d_ids, cn, c.tkeys, c.tvals, 0, c.digests, c.cand, b->d_status);
-        if (list)
-            hipLaunchKernelGGL((bank_seq_mark_kernel<true, true>), grid, block, 0, s, b->g, sw, d_ids, cn, c.tkeys, c.tvals,
-                               0, c.digests, c.cand, d_out8, *list);
-        else
-            hipLaunchKernelGGL(bank_seq_mark_kernel<true>, grid, block, 0, s, b->g, sw, d_ids, cn, c.tkeys, c.tvals, 0,
-                               c.digests, c.cand, d_out8, BankList<false>{});
-    } else {
-        hipLaunchKernelGGL(bank_seq_candidates_kernel<false>, grid, block, 0, s, b->g, b->n_filters, sw, k16, d_off, bias,
-                           d_ids, cn, c.tkeys, c.tvals, c.slots - 1, c.digests, c.cand, b->d_status);
-        if (list)
-            hipLaunchKernelGGL((bank_seq_mark_kernel<false, true>), grid, block, 0, s, b->g, sw, d_ids, cn, c.tkeys,
-                               c.tvals, c.slots - 1, c.digests, c.cand, d_out8, *list);
-        else
-            hipLaunchKernelGGL(bank_seq_mark_kernel<false>, grid, block, 0, s, b->g, sw, d_ids, cn, c.tkeys, c.tvals,
-                               c.slots - 1, c.digests, c.cand, d_out8, BankList<false>{});
-    }
+    const uint64_t sw = b->stride / 4, tmask = direct ? 0 : c.slots - 1;
+#define BF_SEQ_MARK(DIRECT, LIST, list_arg)                                                                           \
+    hipLaunchKernelGGL((bank_seq_mark_kernel<DIRECT, LIST>), grid, block, 0, s, b->g, sw, d_ids, cn, c.tkeys, c.tvals, \
+                       tmask, c.digests, c.cand, d_out8, list_arg)
+#define BF_SEQ_LAUNCH(DIRECT)                                                                                          \
+    do {                                                                                                               \
+        hipLaunchKernelGGL(bank_seq_candidates_kernel<DIRECT>, grid, block, 0, s, b->g, b->n_filters, sw, k16, d_off,  \
+                           bias, d_ids, cn, c.tkeys, c.tvals, tmask, c.digests, c.cand, b->d_status);                  \
+        if (list) BF_SEQ_MARK(DIRECT, true, *list);                                                                    \
+        else BF_SEQ_MARK(DIRECT, false, BankList<false>{});                                                            \
+    } while (0)
+    if (direct) BF_SEQ_LAUNCH(true);
+    else BF_SEQ_LAUNCH(false);
+#undef BF_SEQ_LAUNCH
+#undef BF_SEQ_MARK
     HIPCHK(b, hipGetLastError());
     return BF_OK;
 }
@@ -1244,15 +1298,13 @@ int launch_seq_chunk(bf_bank* b, bool direct, const uint8_t* d_keys, const uint6
 // chunk's list entries (list != NULL) added behind the ones before through the one counter.
 int seq_dev_chunks(bf_bank* b, const uint8_t* d_keys, const uint64_t* d_off, const uint32_t* d_ids, uint64_t n,
                    uint8_t* d_out8, hipStream_t s, const BankList<true>* list) {
-    const uint64_t chunk = bf_seq_chunk_keys(b->k);
-    const bool direct = seq_direct(b, std::min<uint64_t>(n, chunk));
-    // synchronises only when the scratch has to grow
-    int rc = ensure_seq_scratch(b, seq_scratch_bytes(b, direct, std::min<uint64_t>(n, chunk)));
+    const BankSeqPlan plan = seq_plan(b, n, UINT64_MAX);
+    int rc = ensure_seq_scratch(b, plan.scratch);   // synchronises only when the scratch has to grow
     if (rc) return rc;
     // offsets[0] need not be 0, so d_off + a is the offsets array of the keys from a on
-    for (uint64_t a = 0; a < n; a += chunk) {
-        const uint64_t cn = std::min<uint64_t>(n - a, chunk);
-        if ((rc = launch_seq_chunk(b, direct, d_keys, d_off + a, d_ids + a, cn, d_out8 ? d_out8 + a : nullptr, s, list)))
+    for (uint64_t a = 0; a < n; a += plan.chunk) {
+        const uint64_t cn = std::min<uint64_t>(n - a, plan.chunk);
+        if ((rc = launch_seq_chunk(b, plan.direct, d_keys, d_off + a, d_ids + a, cn, d_out8 ? d_out8 + a : nullptr, s, list)))
             return rc;
     }
     return BF_OK;
@@ -1274,12 +1326,7 @@ int check_list(bf_bank* b, const uint32_t* ids, uint64_t count, bool host_ids) {
                             (unsigned long long)b->n_filters, (unsigned long long)count);
         return BF_OK;
     }
-    if (host_ids)
-        for (uint64_t i = 0; i < count; ++i)
-            if ((uint64_t)ids[i] >= b->n_filters)
-                return bank_err(b, BF_EINVAL, "ids[%llu] = %u is not below n_filters = %llu", (unsigned long long)i, ids[i],
-                                (unsigned long long)b->n_filters);
-    return BF_OK;
+    return host_ids ? check_ids(b, "ids", ids, count) : BF_OK;
 }
 
 // A host id list on the device (NULL stays NULL).
@@ -1310,6 +1357,23 @@ int launch_across(bf_bank* b, const uint8_t* d_keys, const uint64_t* d_off, uint
                        bias, d_ids, count, n, across_row_bytes(count) / 8, reinterpret_cast<unsigned long long*>(d_mask),
                        b->d_status);
     HIPCHK(b, hipGetLastError());
+    return BF_OK;
+}
+
+int launch_bitcount(bf_bank* b, const uint32_t* d_ids, uint64_t count, uint64_t* d_out, hipStream_t s) {
+    hipLaunchKernelGGL(bank_bitcount_kernel, dim3(owned_grid(b->stride, count)), dim3(kBankLanes), 0, s,
+                       reinterpret_cast<const uint4*>(b->g.bits), b->stride / 16, b->n_filters, d_ids, count,
+                       reinterpret_cast<unsigned long long*>(d_out), b->d_status);
+    HIPCHK(b, hipGetLastError());
+    return BF_OK;
+}
+
+// Export and import stage count filters as [count * stride bytes | count lengths]: *data is the
+// bytes of the first part, *total of both.
+int io_bytes(bf_bank* b, uint64_t count, uint64_t* data, uint64_t* total) {
+    if (__builtin_mul_overflow(count, b->stride, data) || __builtin_add_overflow(*data, count * 8, total))
+        return bank_err(b, BF_EINVAL, "%llu filters of %llu bytes overflow a 64-bit byte size", (unsigned long long)count,
+                        (unsigned long long)b->stride);
     return BF_OK;
 }
 
@@ -1584,11 +1648,10 @@ int bf_bank_set_seq_form(bf_bank* b, uint32_t form) {
 
 int bf_bank_seq_plan(const bf_bank* b, uint64_t n, uint32_t* direct, uint64_t* chunk_keys, uint64_t* scratch_bytes) {
     if (!b) return BF_EINVAL;
-    const uint64_t cn = std::min<uint64_t>(n, bf_seq_chunk_keys(b->k));
-    const bool d = seq_direct(b, cn);
-    if (direct) *direct = d ? 1u : 0u;
-    if (chunk_keys) *chunk_keys = cn;
-    if (scratch_bytes) *scratch_bytes = cn ? seq_scratch_bytes(b, d, cn) : 0;
+    const BankSeqPlan plan = seq_plan(b, n, UINT64_MAX);
+    if (direct) *direct = plan.direct ? 1u : 0u;
+    if (chunk_keys) *chunk_keys = plan.chunk;
+    if (scratch_bytes) *scratch_bytes = plan.scratch;
     return BF_OK;
 }
 
@@ -1600,33 +1663,17 @@ int bf_bank_insert_many_seq(bf_bank* b, const uint8_t* key_bytes, const uint64_t
     int rc = check_batch(b, key_bytes, offsets, filter_ids, n);
     if (rc) return rc;
     if (int orc = cs.open(b->stream)) return orc;
-    // the form is the call's (bf_bank_seq_plan); run_host's chunks, bounded again by the index width
-    const uint64_t seq_chunk = bf_seq_chunk_keys(b->k);
-    const bool direct = seq_direct(b, std::min<uint64_t>(n, seq_chunk));
-    const uint64_t max_keys = std::min<uint64_t>(b->batch_keys, seq_chunk);
-    if ((rc = ensure_seq_scratch(b, seq_scratch_bytes(b, direct, std::min<uint64_t>(n, max_keys))))) return rc;
-    std::vector<uint64_t> rebased;
-    uint64_t a = 0;
-    while (a < n) {
-        uint64_t e = std::min<uint64_t>(n, a + max_keys);
-        if (offsets[e] - offsets[a] > b->batch_bytes) {
-            e = (uint64_t)(std::upper_bound(offsets + a, offsets + e + 1, offsets[a] + b->batch_bytes) - offsets) - 1;
-            if (e <= a) e = a + 1;
-        }
-        const uint64_t cn = e - a, nbytes = offsets[e] - offsets[a];
-        if ((rc = ensure_keys_io(b, nbytes, cn))) return rc;
-        rebased.resize(cn + 1);
-        for (uint64_t j = 0; j <= cn; ++j) rebased[j] = offsets[a + j] - offsets[a];
-        if (nbytes) HIPCHK(b, hipMemcpyAsync(b->d_keys, key_bytes + offsets[a], nbytes, hipMemcpyHostToDevice, b->stream));
-        HIPCHK(b, hipMemsetAsync(b->d_keys + nbytes, 0, 16, b->stream));
-        HIPCHK(b, hipMemcpyAsync(b->d_off, rebased.data(), (cn + 1) * 8, hipMemcpyHostToDevice, b->stream));
-        HIPCHK(b, hipMemcpyAsync(b->d_ids, filter_ids + a, cn * 4, hipMemcpyHostToDevice, b->stream));
-        if ((rc = launch_seq_chunk(b, direct, b->d_keys, b->d_off, b->d_ids, cn, per_key_new ? b->d_out : nullptr,
+    const BankSeqPlan plan = seq_plan(b, n, b->batch_keys);
+    if ((rc = ensure_seq_scratch(b, plan.scratch))) return rc;
+    std::vector<uint64_t> h_off;   // stage_chunk's, read by its copy until the synchronise
+    for (uint64_t a = 0, e; a < n; a = e) {
+        e = chunk_end(b, offsets, n, a, plan.chunk);
+        if ((rc = stage_chunk(b, key_bytes, offsets, filter_ids, a, e, h_off))) return rc;
+        if ((rc = launch_seq_chunk(b, plan.direct, b->d_keys, b->d_off, b->d_ids, e - a, per_key_new ? b->d_out : nullptr,
                                    b->stream)))
             return rc;
-        if (per_key_new) HIPCHK(b, hipMemcpyAsync(per_key_new + a, b->d_out, cn, hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(b, hipStreamSynchronize(b->stream));   // the staging buffers and `rebased` are free again
-        a = e;
+        if (per_key_new) HIPCHK(b, hipMemcpyAsync(per_key_new + a, b->d_out, e - a, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(b, hipStreamSynchronize(b->stream));   // the staging buffers are free again
     }
     return BF_OK;
 }
@@ -1656,41 +1703,32 @@ int bf_bank_insert_many_changes(bf_bank* b, const uint8_t* key_bytes, const uint
     int rc = check_batch(b, key_bytes, offsets, filter_ids, n);
     if (rc) return rc;
     if (int orc = cs.open(b->stream)) return orc;
-    // run_host's chunks; seq: bf_bank_insert_many_seq's form, chunk bound and scratch
-    const uint64_t seq_chunk = bf_seq_chunk_keys(b->k);
-    const uint64_t max_keys = seq ? std::min<uint64_t>(b->batch_keys, seq_chunk) : b->batch_keys;
-    const bool direct = seq && seq_direct(b, std::min<uint64_t>(n, seq_chunk));
-    if (seq && (rc = ensure_seq_scratch(b, seq_scratch_bytes(b, direct, std::min<uint64_t>(n, max_keys))))) return rc;
-    std::vector<uint64_t> rebased;
+    // seq: bf_bank_insert_many_seq's form, chunk bound and scratch; else chunks of batch_keys keys
+    BankSeqPlan plan{false, b->batch_keys, 0};
+    if (seq) {
+        plan = seq_plan(b, n, b->batch_keys);
+        if ((rc = ensure_seq_scratch(b, plan.scratch))) return rc;
+    }
     std::vector<uint8_t> back;
-    uint64_t a = 0, total = 0, written = 0;
-    while (a < n) {
-        uint64_t e = std::min<uint64_t>(n, a + max_keys);
-        if (offsets[e] - offsets[a] > b->batch_bytes) {
-            e = (uint64_t)(std::upper_bound(offsets + a, offsets + e + 1, offsets[a] + b->batch_bytes) - offsets) - 1;
-            if (e <= a) e = a + 1;
-        }
-        const uint64_t cn = e - a, nbytes = offsets[e] - offsets[a];
+    uint64_t total = 0, written = 0;
+    std::vector<uint64_t> h_off;   // stage_chunk's, read by its copy until the synchronise
+    for (uint64_t a = 0, e; a < n; a = e) {
+        e = chunk_end(b, offsets, n, a, plan.chunk);
+        const uint64_t cn = e - a;
         // the chunk lists into the bank's scratch: what the caller's arrays still hold, at most a
         // probe per entry
         uint64_t entries = cap - written;
         if (entries / b->k >= cn) entries = cn * b->k;
         if (entries > (UINT64_MAX - 8) / 12) return bank_err(b, BF_ENOMEM, "a list of %llu entries", (unsigned long long)entries);
-        if ((rc = ensure_keys_io(b, nbytes, cn))) return rc;
+        if ((rc = stage_chunk(b, key_bytes, offsets, filter_ids, a, e, h_off))) return rc;
         if ((rc = grow(b, (void**)&b->d_chg, &b->chg_cap, chg_bytes(entries)))) return rc;
         unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(b->d_chg);
         uint64_t* d_bits = reinterpret_cast<uint64_t*>(b->d_chg + 8);
         uint32_t* d_lids = reinterpret_cast<uint32_t*>(b->d_chg + 8 + entries * 8);
         const BankList<true> list{d_lids, d_bits, entries, d_cnt};
-        rebased.resize(cn + 1);
-        for (uint64_t j = 0; j <= cn; ++j) rebased[j] = offsets[a + j] - offsets[a];
-        if (nbytes) HIPCHK(b, hipMemcpyAsync(b->d_keys, key_bytes + offsets[a], nbytes, hipMemcpyHostToDevice, b->stream));
-        HIPCHK(b, hipMemsetAsync(b->d_keys + nbytes, 0, 16, b->stream));
-        HIPCHK(b, hipMemcpyAsync(b->d_off, rebased.data(), (cn + 1) * 8, hipMemcpyHostToDevice, b->stream));
-        HIPCHK(b, hipMemcpyAsync(b->d_ids, filter_ids + a, cn * 4, hipMemcpyHostToDevice, b->stream));
         HIPCHK(b, hipMemsetAsync(d_cnt, 0, 8, b->stream));
         uint8_t* d_flags = flags ? b->d_out : nullptr;
-        if (seq) rc = launch_seq_chunk(b, direct, b->d_keys, b->d_off, b->d_ids, cn, d_flags, b->stream, &list);
+        if (seq) rc = launch_seq_chunk(b, plan.direct, b->d_keys, b->d_off, b->d_ids, cn, d_flags, b->stream, &list);
         else rc = launch_keys(b, BANK_INSERT, b->d_keys, b->d_off, b->d_ids, cn, d_flags, b->stream, &list);
         if (rc) return rc;
         if (flags) HIPCHK(b, hipMemcpyAsync(flags + a, b->d_out, cn, hipMemcpyDeviceToHost, b->stream));
@@ -1702,7 +1740,7 @@ int bf_bank_insert_many_changes(bf_bank* b, const uint8_t* key_bytes, const uint
         } else {
             HIPCHK(b, hipMemcpyAsync(&flipped, d_cnt, 8, hipMemcpyDeviceToHost, b->stream));
         }
-        HIPCHK(b, hipStreamSynchronize(b->stream));   // the staging buffers and `rebased` are free again
+        HIPCHK(b, hipStreamSynchronize(b->stream));   // the staging buffers are free again
         if (one_copy) memcpy(&flipped, back.data(), 8);
         const uint64_t got = std::min<uint64_t>(flipped, entries);   // this chunk's entries behind the earlier ones
         if (got && one_copy) {
@@ -1715,7 +1753,6 @@ int bf_bank_insert_many_changes(bf_bank* b, const uint8_t* key_bytes, const uint
         }
         written += got;
         total += flipped;
-        a = e;
     }
     *count = total;
     if (total > cap)
@@ -1734,9 +1771,9 @@ int bf_bank_insert_many_changes_dev(bf_bank* b, const uint8_t* d_key_bytes, cons
     if (seq > 1) return bank_err(b, BF_EINVAL, "seq must be 0 or 1, got %u", seq);
     if (!d_count || (cap && (!d_out_ids || !d_out_bits)) || (n && (!d_key_bytes || !d_offsets || !d_filter_ids)))
         return bank_err(b, BF_EINVAL, "NULL device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_out_bits) & 7u) || (reinterpret_cast<uintptr_t>(d_count) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_out_ids) & 3u))
-        return bank_err(b, BF_EINVAL, "misaligned device pointer (d_out_bits and d_count: 8 bytes, d_out_ids: 4)");
+    if (int arc = check_aligned(b, addr(d_out_bits) | addr(d_count), addr(d_out_ids),
+                                "d_out_bits and d_count: 8 bytes, d_out_ids: 4"))
+        return arc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (int orc = cs.open(s)) return orc;
     HIPCHK(b, hipMemsetAsync(d_count, 0, 8, s));   // the kernels of every chunk add to it
@@ -1759,13 +1796,9 @@ int bf_bank_include_across(bf_bank* b, const uint8_t* key_bytes, const uint64_t*
     CallScope cs(b);
     if (!mask) return bank_err(b, BF_EINVAL, "mask is NULL");
     if (!offsets || (!key_bytes && offsets[n] != offsets[0])) return bank_err(b, BF_EINVAL, "NULL keys / offsets");
-    const uint64_t lo = offsets[0], hi = offsets[n];
-    for (uint64_t j = 0; j < n; ++j)
-        if (!key_ok(lo, offsets[j], offsets[j + 1], hi, nullptr))
-            return bank_err(b, BF_EINVAL, "key %llu: offsets must be non-decreasing and every key below 2 GiB",
-                            (unsigned long long)j);
-    int rc = check_list(b, ids, count, true);
+    int rc = check_keys(b, offsets, nullptr, n);
     if (rc) return rc;
+    if ((rc = check_list(b, ids, count, true))) return rc;
     const uint64_t row = across_row_bytes(count);
     uint64_t total = 0;
     if (__builtin_mul_overflow(n, row, &total))
@@ -1774,28 +1807,16 @@ int bf_bank_include_across(bf_bank* b, const uint8_t* key_bytes, const uint64_t*
     if (int orc = cs.open(b->stream)) return orc;
     const uint32_t* d_ids = nullptr;
     if ((rc = stage_list(b, ids, count, &d_ids))) return rc;
-    // run_host's chunks, bounded again so that the staged mask stays under kAcrossMaskCap
-    const uint64_t max_rows = std::max<uint64_t>(1, kAcrossMaskCap / row);
-    std::vector<uint64_t> rebased;
-    uint64_t a = 0;
-    while (a < n) {
-        uint64_t e = std::min<uint64_t>(n, a + std::min<uint64_t>(b->batch_keys, max_rows));
-        if (offsets[e] - offsets[a] > b->batch_bytes) {
-            e = (uint64_t)(std::upper_bound(offsets + a, offsets + e + 1, offsets[a] + b->batch_bytes) - offsets) - 1;
-            if (e <= a) e = a + 1;
-        }
-        const uint64_t cn = e - a, nbytes = offsets[e] - offsets[a];
-        if ((rc = ensure_keys_io(b, nbytes, cn))) return rc;
-        if ((rc = grow(b, (void**)&b->d_io, &b->io_cap, cn * row))) return rc;
-        rebased.resize(cn + 1);
-        for (uint64_t j = 0; j <= cn; ++j) rebased[j] = offsets[a + j] - offsets[a];
-        if (nbytes) HIPCHK(b, hipMemcpyAsync(b->d_keys, key_bytes + offsets[a], nbytes, hipMemcpyHostToDevice, b->stream));
-        HIPCHK(b, hipMemsetAsync(b->d_keys + nbytes, 0, 16, b->stream));
-        HIPCHK(b, hipMemcpyAsync(b->d_off, rebased.data(), (cn + 1) * 8, hipMemcpyHostToDevice, b->stream));
-        if ((rc = launch_across(b, b->d_keys, b->d_off, cn, d_ids, count, b->d_io, b->stream))) return rc;
-        HIPCHK(b, hipMemcpyAsync(mask + a * row, b->d_io, cn * row, hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(b, hipStreamSynchronize(b->stream));   // the staging buffers, `rebased` and `ids` are free again
-        a = e;
+    // chunks of batch_keys keys, bounded again so that the staged mask stays under kAcrossMaskCap
+    const uint64_t max_keys = std::min<uint64_t>(b->batch_keys, std::max<uint64_t>(1, kAcrossMaskCap / row));
+    std::vector<uint64_t> h_off;   // stage_chunk's, read by its copy until the synchronise
+    for (uint64_t a = 0, e; a < n; a = e) {
+        e = chunk_end(b, offsets, n, a, max_keys);
+        if ((rc = stage_chunk(b, key_bytes, offsets, nullptr, a, e, h_off))) return rc;
+        if ((rc = grow(b, (void**)&b->d_io, &b->io_cap, (e - a) * row))) return rc;
+        if ((rc = launch_across(b, b->d_keys, b->d_off, e - a, d_ids, count, b->d_io, b->stream))) return rc;
+        HIPCHK(b, hipMemcpyAsync(mask + a * row, b->d_io, (e - a) * row, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(b, hipStreamSynchronize(b->stream));   // the staging buffers and `ids` are free again
     }
     return BF_OK;
 }
@@ -1806,11 +1827,9 @@ int bf_bank_include_across_dev(bf_bank* b, const uint8_t* d_key_bytes, const uin
     if (n == 0 || count == 0) return BF_OK;
     CallScope cs(b);
     if (!d_key_bytes || !d_offsets || !d_mask) return bank_err(b, BF_EINVAL, "NULL device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_offsets) & 7u) || (reinterpret_cast<uintptr_t>(d_mask) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_ids) & 3u))
-        return bank_err(b, BF_EINVAL, "misaligned device pointer (d_offsets and d_mask: 8 bytes, d_ids: 4)");
-    int rc = check_list(b, d_ids, count, false);
+    int rc = check_aligned(b, addr(d_offsets) | addr(d_mask), addr(d_ids), "d_offsets and d_mask: 8 bytes, d_ids: 4");
     if (rc) return rc;
+    if ((rc = check_list(b, d_ids, count, false))) return rc;
     uint64_t total = 0;
     if (__builtin_mul_overflow(n, across_row_bytes(count), &total))
         return bank_err(b, BF_EINVAL, "%llu mask rows of %llu bytes overflow a 64-bit byte size", (unsigned long long)n,
@@ -1851,11 +1870,7 @@ int bf_bank_bitcount_dev(bf_bank* b, const uint32_t* d_ids, uint64_t count, uint
     if (!d_out) return bank_err(b, BF_EINVAL, "d_out is NULL");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (int orc = cs.open(s)) return orc;
-    hipLaunchKernelGGL(bank_bitcount_kernel, dim3(owned_grid(b->stride, count)), dim3(kBankLanes), 0, s,
-                       reinterpret_cast<const uint4*>(b->g.bits), b->stride / 16, b->n_filters, d_ids, count,
-                       reinterpret_cast<unsigned long long*>(d_out), b->d_status);
-    HIPCHK(b, hipGetLastError());
-    return BF_OK;
+    return launch_bitcount(b, d_ids, count, d_out, s);
 }
 
 int bf_bank_bitcount(bf_bank* b, const uint32_t* ids, uint64_t count, uint64_t* out) {
@@ -1869,10 +1884,7 @@ int bf_bank_bitcount(bf_bank* b, const uint32_t* ids, uint64_t count, uint64_t* 
     const uint32_t* d_ids = nullptr;
     if ((rc = stage_list(b, ids, count, &d_ids))) return rc;
     if ((rc = grow(b, (void**)&b->d_io, &b->io_cap, count * 8))) return rc;
-    hipLaunchKernelGGL(bank_bitcount_kernel, dim3(owned_grid(b->stride, count)), dim3(kBankLanes), 0, b->stream,
-                       reinterpret_cast<const uint4*>(b->g.bits), b->stride / 16, b->n_filters, d_ids, count,
-                       reinterpret_cast<unsigned long long*>(b->d_io), b->d_status);
-    HIPCHK(b, hipGetLastError());
+    if ((rc = launch_bitcount(b, d_ids, count, reinterpret_cast<uint64_t*>(b->d_io), b->stream))) return rc;
     HIPCHK(b, hipMemcpyAsync(out, b->d_io, count * 8, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(b, hipStreamSynchronize(b->stream));
     return BF_OK;
@@ -1886,9 +1898,7 @@ int bf_bank_export_filters(bf_bank* b, const uint32_t* ids, uint64_t count, uint
     if (count == 0) return BF_OK;
     if (!buf || !lens) return bank_err(b, BF_EINVAL, "buf / lens is NULL");
     uint64_t data = 0, total = 0;
-    if (__builtin_mul_overflow(count, b->stride, &data) || __builtin_add_overflow(data, count * 8, &total))
-        return bank_err(b, BF_EINVAL, "%llu filters of %llu bytes overflow a 64-bit byte size", (unsigned long long)count,
-                        (unsigned long long)b->stride);
+    if ((rc = io_bytes(b, count, &data, &total))) return rc;
     if (int orc = cs.open(b->stream)) return orc;
     const uint32_t* d_ids = nullptr;
     if ((rc = stage_list(b, ids, count, &d_ids))) return rc;
@@ -1924,9 +1934,7 @@ int bf_bank_import_filters(bf_bank* b, const uint32_t* ids, uint64_t count, cons
                             (unsigned long long)b->reach);
     }
     uint64_t data = 0, total = 0;
-    if (__builtin_mul_overflow(count, b->stride, &data) || __builtin_add_overflow(data, count * 8, &total))
-        return bank_err(b, BF_EINVAL, "%llu filters of %llu bytes overflow a 64-bit byte size", (unsigned long long)count,
-                        (unsigned long long)b->stride);
+    if ((rc = io_bytes(b, count, &data, &total))) return rc;
     if (int orc = cs.open(b->stream)) return orc;
     const uint32_t* d_ids = nullptr;
     if ((rc = stage_list(b, ids, count, &d_ids))) return rc;
@@ -1966,19 +1974,12 @@ int bf_bank_fold(bf_bank* b, uint32_t op, const uint32_t* dst_ids, const uint64_
     }
     if (groups == 0) return BF_OK;
     const uint64_t n_src = seg[groups];
-    for (uint64_t i = 0; i < n_src; ++i)
-        if ((uint64_t)src_ids[i] >= b->n_filters)
-            return bank_err(b, BF_EINVAL, "src_ids[%llu] = %u is not below n_filters = %llu", (unsigned long long)i,
-                            src_ids[i], (unsigned long long)b->n_filters);
+    if ((rc = check_ids(b, "src_ids", src_ids, n_src))) return rc;
     if (dst_ids) {
+        if ((rc = check_ids(b, "dst_ids", dst_ids, groups))) return rc;
         // a destination is written by one group and read by no other: sorted (id, group) pairs
         std::vector<std::pair<uint32_t, uint64_t>> owner(groups);
-        for (uint64_t g = 0; g < groups; ++g) {
-            if ((uint64_t)dst_ids[g] >= b->n_filters)
-                return bank_err(b, BF_EINVAL, "dst_ids[%llu] = %u is not below n_filters = %llu", (unsigned long long)g,
-                                dst_ids[g], (unsigned long long)b->n_filters);
-            owner[g] = {dst_ids[g], g};
-        }
+        for (uint64_t g = 0; g < groups; ++g) owner[g] = {dst_ids[g], g};
         std::sort(owner.begin(), owner.end());
         uint64_t twice = UINT64_MAX;   // the first group (in list order) whose destination an earlier group has
         for (uint64_t i = 1; i < groups; ++i)
@@ -2029,9 +2030,9 @@ int bf_bank_fold_dev(bf_bank* b, uint32_t op, const uint32_t* d_dst_ids, const u
     if (rc) return rc;
     if (groups == 0) return BF_OK;
     if (!d_seg || !d_src_ids) return bank_err(b, BF_EINVAL, "NULL device pointer (d_seg / d_src_ids)");
-    if ((reinterpret_cast<uintptr_t>(d_seg) & 7u) || (reinterpret_cast<uintptr_t>(d_set_bits) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_src_ids) & 3u) || (reinterpret_cast<uintptr_t>(d_dst_ids) & 3u))
-        return bank_err(b, BF_EINVAL, "misaligned device pointer (d_seg and d_set_bits: 8 bytes, d_src_ids and d_dst_ids: 4)");
+    if ((rc = check_aligned(b, addr(d_seg) | addr(d_set_bits), addr(d_src_ids) | addr(d_dst_ids),
+                            "d_seg and d_set_bits: 8 bytes, d_src_ids and d_dst_ids: 4")))
+        return rc;
     if (groups > (1ull << 56)) return bank_err(b, BF_EINVAL, "too many groups");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (int orc = cs.open(s)) return orc;
@@ -2047,14 +2048,8 @@ int bf_bank_overlap(bf_bank* b, const uint32_t* row_ids, uint64_t rows, const ui
     int rc = check_overlap(b, row_ids, rows, col_ids, cols, &out_bytes);
     if (rc) return rc;
     if (!out) return bank_err(b, BF_EINVAL, "out is NULL");
-    for (uint64_t i = 0; row_ids && i < rows; ++i)
-        if ((uint64_t)row_ids[i] >= b->n_filters)
-            return bank_err(b, BF_EINVAL, "row_ids[%llu] = %u is not below n_filters = %llu", (unsigned long long)i,
-                            row_ids[i], (unsigned long long)b->n_filters);
-    for (uint64_t i = 0; col_ids && i < cols; ++i)
-        if ((uint64_t)col_ids[i] >= b->n_filters)
-            return bank_err(b, BF_EINVAL, "col_ids[%llu] = %u is not below n_filters = %llu", (unsigned long long)i,
-                            col_ids[i], (unsigned long long)b->n_filters);
+    if (row_ids && (rc = check_ids(b, "row_ids", row_ids, rows))) return rc;
+    if (col_ids && (rc = check_ids(b, "col_ids", col_ids, cols))) return rc;
     if (int orc = cs.open(b->stream)) return orc;
     // both lists side by side in d_list; without col_ids the columns are the row list
     const uint64_t n_row = row_ids ? rows : 0, n_col = col_ids ? cols : 0;
@@ -2089,9 +2084,8 @@ int bf_bank_overlap_dev(bf_bank* b, const uint32_t* d_row_ids, uint64_t rows, co
     int rc = check_overlap(b, d_row_ids, rows, d_col_ids, cols, &out_bytes);
     if (rc) return rc;
     if (!d_out) return bank_err(b, BF_EINVAL, "NULL device pointer (d_out)");
-    if ((reinterpret_cast<uintptr_t>(d_out) & 7u) || (reinterpret_cast<uintptr_t>(d_row_ids) & 3u) ||
-        (reinterpret_cast<uintptr_t>(d_col_ids) & 3u))
-        return bank_err(b, BF_EINVAL, "misaligned device pointer (d_out: 8 bytes, d_row_ids and d_col_ids: 4)");
+    if ((rc = check_aligned(b, addr(d_out), addr(d_row_ids) | addr(d_col_ids), "d_out: 8 bytes, d_row_ids and d_col_ids: 4")))
+        return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (int orc = cs.open(s)) return orc;
     return launch_overlap(b, d_row_ids, 0, rows, d_col_ids ? d_col_ids : d_row_ids, cols, !d_col_ids, d_out, s);
