@@ -1,10 +1,10 @@
 // bf_api.cpp — the C ABI declared in include/bfhip.h.
 //
-// Owns the device bitset (one HIP device per handle), a HIP stream, and two
+// Owns the device bitset (one HIP device per handle), a HIP stream, and three
 // staging slots (pinned host + device) used by the host-pointer calls so that
-// packing chunk c+1 on the host overlaps the device work of chunk c.
+// staging chunk c+2 on the host overlaps the H2D of chunk c+1 and the kernels of chunk c.
 #include "bfhip.h"
-#include "bf_internal.h"
+#include "bf_host.h"
 #include "bf_multi.h"
 #include "bf_device.h"   // bfdev::key_ok: bf_check_offsets applies the kernels' rule
 
@@ -16,7 +16,6 @@
 #include <condition_variable>
 #include <functional>
 #include <thread>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -139,10 +138,7 @@ constexpr int kSlots = 3;   // host staging of chunk c+2 || H2D of c+1 || kernel
 
 }  // namespace
 
-struct bf_handle {
-    std::mutex mu;
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct bf_handle : BfHostCore {
     BfGeom g{};
     uint64_t m = 0, reach = 0, dev_bytes = 0;
     uint32_t k = 0;
@@ -196,97 +192,46 @@ struct bf_handle {
     // incremental Redis sync (bf_track_dirty): one byte per BF_DIRTY_BLOCK_BYTES of the string
     uint8_t* d_dirty = nullptr;
     uint64_t dirty_blocks = 0;
-    // per-kernel timing (bf_profile): event sets awaiting harvest, recycled sets, totals
-    bool profile = false;
-    std::vector<BfMarks> prof_pending, prof_free;
-    struct ProfAcc { std::string name; double ms; uint64_t launches; };
-    std::vector<ProfAcc> prof_acc;
-    // cross-stream ordering (StreamOrder): the event after the handle's last device work
-    hipEvent_t order_ev = nullptr;
-    hipStream_t order_stream = nullptr;
-    bool order_valid = false;
     BfMulti* multi = nullptr;   // a multi-device handle (bf_config.device_count > 0): bf_multi.cpp
-    std::string err;
 };
 
 namespace {
 
-// Orders one handle's device work across streams.  Every entry point that touches the
-// bitset or the handle's scratch (the binned / sequential arenas, staging, routing
-// scratch) holds one of these around its launches: work arriving on a different stream
-// than the previous call's first waits for that call's last launch (hipStreamWaitEvent,
-// no host sync), so *_dev calls on two streams never race on the shared scratch or on
-// bin_apply's plain region stores.  Calls on one stream pay only an event record.
-// The key-status word (BfGeom::key_status, pinned host memory the kernels write): a hashing
-// kernel of an earlier call met a key whose offsets were inconsistent (offsets not
-// non-decreasing, or a key of 2 GiB or more) and hashed it as the empty key instead of running
-// off the key buffer or looping over a wrapped length (bfdev::key_ok).  The kernels run
-// asynchronously, so the error is reported once, as BF_EINVAL, by the next call on the handle
-// (bf_sync after the call at the latest), as the region-set status is checked lazily.
-int take_key_status(bf_handle* h);
-// Every op's entry check (after its StreamOrder): take_key_status, and a handle created with
-// BF_FLAG_ENCODER (no bitset) refused unless the op needs no bitset (the region-set encodes).
-int op_check(bf_handle* h, bool needs_bits = true);
-
-struct StreamOrder {
-    bf_handle* h;
-    hipStream_t s;
-    StreamOrder(bf_handle* h_, hipStream_t s_) : h(h_), s(s_) {
-        if (h->order_valid && h->order_stream != s) (void)hipStreamWaitEvent(s, h->order_ev, 0);
-    }
-    ~StreamOrder() {
-        if (h->order_ev && hipEventRecord(h->order_ev, s) == hipSuccess) {
-            h->order_valid = true;
-            h->order_stream = s;
-        }
-    }
-    StreamOrder(const StreamOrder&) = delete;
-    StreamOrder& operator=(const StreamOrder&) = delete;
-};
-
-int set_err(bf_handle* h, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf; else g_create_error = buf;
-    return code;
+// h == NULL: a create-time error, read back with bf_last_error(NULL).
+template <typename... A>
+int set_err(bf_handle* h, int code, const char* fmt, A... a) {
+    return bf_set_err(h, &g_create_error, code, fmt, a...);
 }
 
-int op_check(bf_handle* h, bool needs_bits) {
+// The opening refusal of the entry points that take single-device handles only.
+int single_handle(const bf_handle* h) {
+    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
+    return h ? BF_OK : BF_EINVAL;
+}
+
+// Every op's entry check (after its stream is ordered): a handle created with BF_FLAG_ENCODER
+// (no bitset) is refused unless the op needs no bitset (the region-set encodes); then the
+// key-status word.  A hashing kernel of an earlier call that met a key whose offsets were
+// inconsistent hashed it as the empty key (bfdev::key_ok); the kernels run asynchronously, so the
+// error is reported once, as BF_EINVAL, by the next call on the handle (bf_sync at the latest).
+int op_check(bf_handle* h, bool needs_bits = true) {
     if (needs_bits && !h->g.bits)
         return set_err(h, BF_EINVAL, "an encoder handle (BF_FLAG_ENCODER) holds no bitset: region-set encodes only");
-    return take_key_status(h);
+    return take_key_status(h, h->h_key_status);
 }
 
-int take_key_status(bf_handle* h) {
-    if (!h->h_key_status || __atomic_load_n(h->h_key_status, __ATOMIC_ACQUIRE) == 0u) return BF_OK;
-    __atomic_store_n(h->h_key_status, 0u, __ATOMIC_RELEASE);
-    return set_err(h, BF_EINVAL, "an earlier call's key offsets were inconsistent (offsets must be non-decreasing "
-                                 "and every key below 2 GiB): those keys were hashed as empty strings");
+// An entry point's opening, after `CallScope cs(h)` and the argument refusals: the device made
+// current, stream s ordered after the handle's last work (every entry point that touches the
+// bitset or the handle's scratch orders its stream, so *_dev calls on two streams never race on
+// them), then op_check.  A composite call runs several bodies under one scope, each opening it
+// where it always has, after its own refusals: the first opens, orders and checks, the later
+// ones find the scope open and repeat the encoder refusal alone (a key status that an earlier
+// part of the same call raised is left to the next call).
+int handle_open(CallScope& cs, bf_handle* h, hipStream_t s, bool needs_bits = true) {
+    if (cs.so) return needs_bits && !h->g.bits ? op_check(h) : BF_OK;   // (open: the encoder refusal alone)
+    if (int rc = cs.open(s)) return rc;
+    return op_check(h, needs_bits);
 }
-
-#define HIPCHK(h, expr)                                                                      \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return set_err((h), (e_ == hipErrorOutOfMemory ? BF_ENOMEM : BF_EDEVICE),        \
-                           "%s failed: %s", #expr, hipGetErrorString(e_));                   \
-    } while (0)
-
-// Makes the handle's device current for the duration of a call.
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = (prev == dev) || hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
@@ -410,15 +355,19 @@ int check_keys_args(bf_handle* h, const void* keys, const uint64_t* offsets, uin
     return BF_OK;
 }
 
-// Binned insert / include?: worth it when the batch's random line fills (~128 B
-// per probe) clearly exceed one streaming pass over a bitset that lives beyond L2.
+// When a binned pass pays, for the keyed ops and the owner ops alike: by the op's policy knob
+// (0 never, 1 always, else auto), and in auto when the bitset lives beyond L2 and the batch's
+// random line fills (~128 B per probe) clearly exceed one streaming pass over it.
+bool binned_pays(const bf_handle* h, uint32_t mode, double probes) {
+    if (mode == 0) return false;
+    return mode == 1 || (h->dev_bytes >= (64ull << 20) && probes * 128.0 > kBinnedCostRatio * (double)h->dev_bytes);
+}
+
+// Binned insert / include? of n keys: a whole ruby-derivation filter, when it pays and plans.
 bool use_binned(const bf_handle* h, uint64_t n, bool include, BfBinPlan* plan) {
-    const uint32_t mode = include ? h->include_binned_mode : h->binned_mode;
-    if (mode == 0 || h->shards > 1 || h->engine != BF_ENGINE_RUBY) return false;
-    if (!bf_binned_plan(h->dev_bytes, n, h->k, h->bin_region_log2, include, plan)) return false;
-    if (mode == 1) return true;
-    return h->dev_bytes >= (64ull << 20) &&
-           (double)n * (double)h->k * 128.0 > kBinnedCostRatio * (double)h->dev_bytes;
+    if (h->shards > 1 || h->engine != BF_ENGINE_RUBY) return false;
+    return binned_pays(h, include ? h->include_binned_mode : h->binned_mode, (double)n * (double)h->k) &&
+           bf_binned_plan(h->dev_bytes, n, h->k, h->bin_region_log2, include, plan);
 }
 
 // Device scratch shared by the binned and the sequential insert paths (grown on demand).
@@ -431,43 +380,6 @@ int ensure_scratch(bf_handle* h, uint64_t bytes) {
     const uint64_t cap = round_up(bytes, 16ull << 20);
     HIPCHK(h, hipMalloc(&h->d_bin_scratch, cap));
     h->bin_scratch_cap = cap;
-    return BF_OK;
-}
-
-// bf_profile: an event set per keyed launch, harvested by bf_profile_read.
-BfMarks* prof_begin(bf_handle* h, hipStream_t s) {
-    if (!h->profile) return nullptr;
-    BfMarks mk{};
-    if (!h->prof_free.empty()) {
-        mk = h->prof_free.back();
-        h->prof_free.pop_back();
-    } else {
-        for (hipEvent_t& e : mk.ev)
-            if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    }
-    mk.used = 0;
-    if (hipEventRecord(mk.ev[0], s) != hipSuccess) {
-        h->prof_free.push_back(mk);
-        return nullptr;
-    }
-    h->prof_pending.push_back(mk);
-    return &h->prof_pending.back();
-}
-
-int prof_harvest(bf_handle* h) {
-    for (BfMarks& mk : h->prof_pending) {
-        if (mk.used > 0) HIPCHK(h, hipEventSynchronize(mk.ev[mk.used]));
-        for (int i = 0; i < mk.used; ++i) {
-            float ms = 0.f;
-            HIPCHK(h, hipEventElapsedTime(&ms, mk.ev[i], mk.ev[i + 1]));
-            auto it = std::find_if(h->prof_acc.begin(), h->prof_acc.end(),
-                                   [&](const bf_handle::ProfAcc& a) { return a.name == mk.names[i]; });
-            if (it == h->prof_acc.end()) h->prof_acc.push_back({mk.names[i], (double)ms, 1});
-            else { it->ms += ms; it->launches += 1; }
-        }
-        h->prof_free.push_back(mk);
-    }
-    h->prof_pending.clear();
     return BF_OK;
 }
 
@@ -751,30 +663,20 @@ hipStream_t pick_stream(bf_handle*, void* stream) {
     return reinterpret_cast<hipStream_t>(stream);   // verbatim: NULL is the null stream
 }
 
-// Device pointer + 16-byte alignment bias for the kernels.
-const uint8_t* align_keys(const uint8_t* p, uint64_t* bias) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-    *bias = a & 15u;
-    return reinterpret_cast<const uint8_t*>(a & ~(uintptr_t)15);
-}
-
 int run_dev(bf_handle* h, BfOp op, const uint8_t* d_keys, const uint64_t* d_offsets, uint64_t n,
             uint8_t* d_out8, uint64_t* d_out64, uint32_t* d_flag, void* stream) {
-    if (!h) return BF_EINVAL;
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
     if (n == 0) return BF_OK;
     if (!d_offsets || !d_keys) return set_err(h, BF_EINVAL, "NULL device pointer");
     if (op == BF_OP_INCLUDE && !d_out8) return set_err(h, BF_EINVAL, "d_out is NULL");
     if (op == BF_OP_INDEXES && !d_out64) return set_err(h, BF_EINVAL, "d_out is NULL");
     if (op != BF_OP_INDEXES && h->shards > 1)
         return set_err(h, BF_EINVAL, "handle holds one shard of a partitioned filter: use bf_route_dev");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
+    if (int rc = handle_open(cs, h, pick_stream(h, stream))) return rc;
     uint64_t bias = 0;
     const uint8_t* k16 = align_keys(d_keys, &bias);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    return launch_op(h, op, k16, d_offsets, bias, n, d_out8, d_out64, d_flag, so.s);
+    return launch_op(h, op, k16, d_offsets, bias, n, d_out8, d_out64, d_flag, cs.s);
 }
 
 }  // namespace
@@ -1018,8 +920,8 @@ int bf_destroy(bf_handle* h) {
         return BF_OK;
     }
     {
-        std::lock_guard<std::mutex> lk(h->mu);
-        DeviceGuard dg(h->device);
+        CallScope cs(h);
+        DeviceGuard dg(h->device);   // unchecked: the teardown goes on whatever fails
         if (h->order_valid) (void)hipEventSynchronize(h->order_ev);
         if (h->stream) (void)hipStreamSynchronize(h->stream);
         free_staging(h);
@@ -1038,8 +940,7 @@ int bf_destroy(bf_handle* h) {
         if (h->d_seg) (void)hipFree(h->d_seg);
         if (h->d_dirty) (void)hipFree(h->d_dirty);
         (void)prof_harvest(h);   // waits for marks recorded on caller streams
-        for (BfMarks& mk : h->prof_free)
-            for (hipEvent_t e : mk.ev) (void)hipEventDestroy(e);
+        prof_destroy(h);
         if (h->order_ev) (void)hipEventDestroy(h->order_ev);
         if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
         if (h->d2h_stream) (void)hipStreamDestroy(h->d2h_stream);
@@ -1063,12 +964,9 @@ int bf_insert_many(bf_handle* h, const uint8_t* key_bytes, const uint64_t* offse
                    uint8_t* any_new, uint8_t* per_key_new) {
     if (h && h->multi) return bfm_insert_many(h->multi, key_bytes, offsets, n, any_new, per_key_new);
     if (!h) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
+    CallScope cs(h);
     const BfOp op = (any_new || per_key_new) ? BF_OP_INSERT_FLAGS : BF_OP_INSERT;
-    StreamOrder so(h, h->stream);
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
+    if (int krc = handle_open(cs, h, h->stream)) return krc;
     int rc = run_host(h, op, key_bytes, offsets, n, per_key_new, nullptr, any_new);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1078,10 +976,10 @@ int bf_insert_many(bf_handle* h, const uint8_t* key_bytes, const uint64_t* offse
 int bf_insert_many_changes(bf_handle* h, const uint8_t* key_bytes, const uint64_t* offsets, uint64_t n,
                            uint64_t* out_bits, uint64_t cap, uint64_t* count) {
     if (!h) return BF_EINVAL;
+    CallScope cs(h);
     if (!count) return set_err(h, BF_EINVAL, "count is NULL");
     *count = 0;
     if (h->multi) return set_err(h, BF_EINVAL, "bf_insert_many_changes: a multi-device handle (use bf_dirty_ranges)");
-    std::lock_guard<std::mutex> lk(h->mu);
     int rc = check_keys_args(h, key_bytes, offsets, n);
     if (rc) return rc;
     if (n == 0) return BF_OK;
@@ -1092,44 +990,33 @@ int bf_insert_many_changes(bf_handle* h, const uint8_t* key_bytes, const uint64_
     if (!out_bits || cap < n * h->k) return set_err(h, BF_EINVAL, "out_bits must hold n * k offsets");
     for (uint64_t j = 0; j < n; ++j)
         if (offsets[j + 1] < offsets[j]) return set_err(h, BF_EINVAL, "offsets must be non-decreasing");
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, h->stream);
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
+    if (int krc = handle_open(cs, h, h->stream)) return krc;
     return run_small(h, BF_OP_INSERT_FLAGS, key_bytes, offsets, n, nullptr, nullptr, out_bits, count);
 }
 
 int bf_include_many(bf_handle* h, const uint8_t* key_bytes, const uint64_t* offsets, uint64_t n, uint8_t* out) {
     if (h && h->multi) return bfm_include_many(h->multi, key_bytes, offsets, n, out);
     if (!h) return BF_EINVAL;
+    CallScope cs(h);
     if (n && !out) return set_err(h, BF_EINVAL, "out is NULL");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, h->stream);
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
+    if (int krc = handle_open(cs, h, h->stream)) return krc;
     return run_host(h, BF_OP_INCLUDE, key_bytes, offsets, n, out, nullptr, nullptr);
 }
 
 int bf_indexes_many(bf_handle* h, const uint8_t* key_bytes, const uint64_t* offsets, uint64_t n, uint64_t* out) {
     if (h && h->multi) return bfm_indexes_many(h->multi, key_bytes, offsets, n, out);
     if (!h) return BF_EINVAL;
+    CallScope cs(h);
     if (n && !out) return set_err(h, BF_EINVAL, "out is NULL");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, h->stream);
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
+    if (int krc = handle_open(cs, h, h->stream)) return krc;
     return run_host(h, BF_OP_INDEXES, key_bytes, offsets, n, nullptr, out, nullptr);
 }
 
 int bf_clear(bf_handle* h) {
     if (h && h->multi) return bfm_clear(h->multi);
     if (!h) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, h->stream);
+    CallScope cs(h);
+    if (int rc = cs.open(h->stream)) return rc;   // (no op_check: a clear leaves a pending key status to the next op)
     if (!h->g.bits) return set_err(h, BF_EINVAL, "an encoder handle (BF_FLAG_ENCODER) holds no bitset");
     HIPCHK(h, hipMemsetAsync(h->g.bits, 0, h->dev_bytes, h->stream));
     if (h->d_dirty) HIPCHK(h, hipMemsetAsync(h->d_dirty, 0, h->dirty_blocks, h->stream));   // the driver DELs the key
@@ -1140,11 +1027,14 @@ int bf_clear(bf_handle* h) {
 int bf_sync(bf_handle* h) {
     if (h && h->multi) return bfm_sync(h->multi);
     if (!h) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(h->mu);
+    // The calls that only wait or read back take the scope for its mutex and an unchecked
+    // DeviceGuard: they order no stream, and a failed hipSetDevice shows as the failure of the
+    // HIP call that follows.
+    CallScope cs(h);
     DeviceGuard dg(h->device);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (h->order_valid) HIPCHK(h, hipEventSynchronize(h->order_ev));   // the last call, on whatever stream
-    return take_key_status(h);
+    return take_key_status(h, h->h_key_status);
 }
 
 }  // extern "C"
@@ -1152,9 +1042,8 @@ int bf_sync(bf_handle* h) {
 namespace {
 
 // Trimmed length of the first `max_bytes` bytes of the device bitset (Redis STRLEN after SETBITs).
-int device_trimmed_len(bf_handle* h, uint64_t* len_out) {
-    StreamOrder so(h, h->stream);
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
+int device_trimmed_len(CallScope& cs, bf_handle* h, uint64_t* len_out) {
+    if (int krc = handle_open(cs, h, h->stream)) return krc;
     HIPCHK(h, hipMemsetAsync(h->d_scan, 0, sizeof(unsigned long long), h->stream));
     HIPCHK(h, bf_launch_last_nonzero(h->g.bits, h->dev_bytes / 4, h->d_scan, h->stream));
     unsigned long long last = 0;
@@ -1175,7 +1064,8 @@ int device_trimmed_len(bf_handle* h, uint64_t* len_out) {
 }
 
 // Load `len` bytes (device layout) into the bitset; bits at offsets >= max_bits are refused.
-int import_bytes(bf_handle* h, const uint8_t* buf, uint64_t len, uint32_t mode, uint64_t max_bits) {
+int import_bytes(CallScope& cs, bf_handle* h, const uint8_t* buf, uint64_t len, uint32_t mode, uint64_t max_bits) {
+    if (int rc = cs.device()) return rc;
     if (mode != BF_IMPORT_REPLACE && mode != BF_IMPORT_OR) return set_err(h, BF_EINVAL, "bad import mode %u", mode);
     if (len && !buf) return set_err(h, BF_EINVAL, "buf is NULL");
     const uint64_t max_bytes = (max_bits + 7) / 8;
@@ -1187,8 +1077,7 @@ int import_bytes(bf_handle* h, const uint8_t* buf, uint64_t len, uint32_t mode, 
         if (buf[len - 1] & beyond)
             return set_err(h, BF_ERANGE, "string sets bits at offsets >= %llu", (unsigned long long)max_bits);
     }
-    StreamOrder so(h, h->stream);
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
+    if (int krc = handle_open(cs, h, h->stream)) return krc;
     if (h->d_dirty) HIPCHK(h, hipMemsetAsync(h->d_dirty, 1, h->dirty_blocks, h->stream));
     if (mode == BF_IMPORT_REPLACE) {
         HIPCHK(h, hipMemsetAsync(h->g.bits, 0, h->dev_bytes, h->stream));
@@ -1208,6 +1097,16 @@ int import_bytes(bf_handle* h, const uint8_t* buf, uint64_t len, uint32_t mode, 
     (void)hipFree(tmp);
     if (e != hipSuccess) return set_err(h, BF_EDEVICE, "import OR failed: %s", hipGetErrorString(e));
     return BF_OK;
+}
+
+// Bits of the largest shard (index 0 holds ceil(nblocks / P) blocks), and the 2^32-bit
+// sub-ranges its local offsets span (bf_route_window_split).
+uint64_t largest_shard_bits(const bf_handle* h) {
+    const uint64_t nblocks = (h->reach + (1ull << h->block_log2) - 1) >> h->block_log2;
+    return h->shards == 1 ? h->reach : ((nblocks + h->shards - 1) / h->shards) << h->block_log2;
+}
+uint32_t window_split(const bf_handle* h) {
+    return std::max<uint32_t>(1, (uint32_t)((largest_shard_bits(h) + 0xFFFFFFFFull) >> 32));
 }
 
 int ensure_route_scratch(bf_handle* h, uint64_t probes) {
@@ -1233,12 +1132,10 @@ extern "C" {
 int bf_export_redis(bf_handle* h, uint8_t* buf, uint64_t cap, uint64_t* len_out) {
     if (h && h->multi) return len_out ? bfm_export_redis(h->multi, buf, cap, len_out) : BF_EINVAL;
     if (!h || !len_out) return BF_EINVAL;
+    CallScope cs(h);
     if (h->shards > 1) return set_err(h, BF_EINVAL, "partitioned shard: use bf_shard_export and interleave blocks");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
     uint64_t len = 0;
-    int rc = device_trimmed_len(h, &len);
+    int rc = device_trimmed_len(cs, h, &len);
     if (rc) return rc;
     *len_out = len;
     if (!buf) return BF_OK;
@@ -1250,11 +1147,9 @@ int bf_export_redis(bf_handle* h, uint8_t* buf, uint64_t cap, uint64_t* len_out)
 int bf_import_redis(bf_handle* h, const uint8_t* buf, uint64_t len, uint32_t mode) {
     if (h && h->multi) return bfm_import_redis(h->multi, buf, len, mode);
     if (!h) return BF_EINVAL;
+    CallScope cs(h);
     if (h->shards > 1) return set_err(h, BF_EINVAL, "partitioned shard: use bf_shard_import");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    return import_bytes(h, buf, len, mode, h->reach);
+    return import_bytes(cs, h, buf, len, mode, h->reach);
 }
 
 int bf_shard_info(const bf_handle* h, uint32_t* shard_count, uint32_t* shard_index, uint32_t* block_log2,
@@ -1269,15 +1164,14 @@ int bf_shard_info(const bf_handle* h, uint32_t* shard_count, uint32_t* shard_ind
 }
 
 int bf_shard_export(bf_handle* h, uint8_t* buf, uint64_t cap, uint64_t* len_out) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h || !len_out) return BF_EINVAL;
+    if (int rc = single_handle(h)) return rc;
+    if (!len_out) return BF_EINVAL;
+    CallScope cs(h);
     const uint64_t len = (h->local_bits + 7) / 8;
     *len_out = len;
     if (!buf) return BF_OK;
     if (cap < len) return set_err(h, BF_ERANGE, "export buffer too small: need %llu bytes", (unsigned long long)len);
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
+    if (int rc = cs.device()) return rc;   // waits for the handle's work, orders no stream
     if (h->order_valid) HIPCHK(h, hipEventSynchronize(h->order_ev));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (len) HIPCHK(h, hipMemcpy(buf, h->g.bits, len, hipMemcpyDeviceToHost));
@@ -1285,29 +1179,22 @@ int bf_shard_export(bf_handle* h, uint8_t* buf, uint64_t cap, uint64_t* len_out)
 }
 
 int bf_shard_import(bf_handle* h, const uint8_t* buf, uint64_t len, uint32_t mode) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    return import_bytes(h, buf, len, mode, h->local_bits);
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    return import_bytes(cs, h, buf, len, mode, h->local_bits);
 }
 
 int bf_route_dev(bf_handle* h, const uint8_t* d_key_bytes, const uint64_t* d_offsets, uint64_t n,
                  void* d_send, uint32_t* d_slot, uint64_t* d_counts, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
     if (!d_counts) return set_err(h, BF_EINVAL, "d_counts is NULL");
     if (n && (!d_key_bytes || !d_offsets || !d_send)) return set_err(h, BF_EINVAL, "NULL device pointer");
     const uint64_t probes = n * h->k;
     if (n && probes / n != h->k) return set_err(h, BF_EINVAL, "n*k overflows");
     if (probes >= (1ull << 32)) return set_err(h, BF_EINVAL, "n*k must be < 2^32 per call (slot indices are 32-bit)");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    hipStream_t s = so.s;
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
+    hipStream_t s = cs.s;
     auto* counts = reinterpret_cast<unsigned long long*>(d_counts);
     BfBinPlan plan;
     if (h->binned_mode != 0 && bf_route_plan(n, h->k, h->shards, !h->route32, d_slot != nullptr, &plan)) {
@@ -1341,34 +1228,25 @@ int bf_route_dev(bf_handle* h, const uint8_t* d_key_bytes, const uint64_t* d_off
 int bf_route_window_split(const bf_handle* h, uint32_t* nh) {
     if (h && h->multi) return BF_EINVAL;
     if (!h || !nh) return BF_EINVAL;
-    // the largest shard (index 0) holds ceil(nblocks / P) blocks
-    const uint64_t nblocks = (h->reach + (1ull << h->block_log2) - 1) >> h->block_log2;
-    const uint64_t bits0 = h->shards == 1 ? h->reach : ((nblocks + h->shards - 1) / h->shards) << h->block_log2;
-    *nh = (uint32_t)((bits0 + 0xFFFFFFFFull) >> 32);
-    if (*nh == 0) *nh = 1;
+    *nh = window_split(h);
     return BF_OK;
 }
 
 int bf_route_windows_dev(bf_handle* h, const uint8_t* d_key_bytes, const uint64_t* d_offsets, uint64_t n,
                          uint32_t* d_send, uint32_t* d_slot, uint64_t window_cap, uint64_t* d_counts, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
     if (!d_counts) return set_err(h, BF_EINVAL, "d_counts is NULL");
     if (n && (!d_key_bytes || !d_offsets || !d_send)) return set_err(h, BF_EINVAL, "NULL device pointer");
     const uint64_t probes = n * h->k;
     if (n && probes / n != h->k) return set_err(h, BF_EINVAL, "n*k overflows");
     if (probes >= (1ull << 32)) return set_err(h, BF_EINVAL, "n*k must be < 2^32 per call (slot indices are 32-bit)");
-    uint32_t nh = 1;
-    bf_route_window_split(h, &nh);
+    const uint32_t nh = window_split(h);
     const uint32_t nwin = h->shards * nh;
     if (nwin > 256) return set_err(h, BF_EINVAL, "%u shards x %u sub-ranges exceed 256 windows", h->shards, nh);
     if (window_cap && (uint64_t)nwin > ~0ull / window_cap) return set_err(h, BF_EINVAL, "window_cap overflows");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    hipStream_t s = so.s;
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
+    hipStream_t s = cs.s;
     BfBinPlan plan;
     if (n && !bf_route_plan(n, h->k, nwin, false, d_slot != nullptr, &plan))
         return set_err(h, BF_EINVAL, "batch of %llu keys at k=%u over %u windows exceeds one window-route pass",
@@ -1389,10 +1267,8 @@ constexpr uint32_t kL2SweepMaxSupLog2 = 25;   // 4 MiB superbins: what one XCD's
 
 // l2 (nullable): whether the owner's include? takes the L2-local sweep with this geometry.
 static bool handle_chunks(const bf_handle* h, BfChunks* cg, uint32_t* nh_out, bool* l2 = nullptr) {
-    uint32_t nh = 1;
-    bf_route_window_split(h, &nh);
-    const uint64_t nblocks = (h->reach + (1ull << h->block_log2) - 1) >> h->block_log2;
-    const uint64_t bits0 = h->shards == 1 ? h->reach : ((nblocks + h->shards - 1) / h->shards) << h->block_log2;
+    const uint32_t nh = window_split(h);
+    const uint64_t bits0 = largest_shard_bits(h);
     if (nh_out) *nh_out = nh;
     const uint32_t nwin = h->shards * nh;
     bool sweep = false;
@@ -1444,8 +1320,8 @@ namespace {
 int route_chunks_impl(bf_handle* h, const uint8_t* d_key_bytes, const uint64_t* d_offsets, uint64_t n, bool dig,
                       uint32_t* d_send, uint16_t* d_slot16, uint64_t window_cap, uint64_t* d_counts, uint8_t* d_dir,
                       uint64_t dir_bytes, uint64_t tiles, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
     if (!d_counts || !d_dir) return set_err(h, BF_EINVAL, "d_counts / d_dir is NULL");
     if (n && (!d_key_bytes || (!dig && !d_offsets) || !d_send)) return set_err(h, BF_EINVAL, "NULL device pointer");
     if (dig && n && (reinterpret_cast<uintptr_t>(d_key_bytes) & 15u))
@@ -1464,12 +1340,8 @@ int route_chunks_impl(bf_handle* h, const uint8_t* d_key_bytes, const uint64_t* 
         return set_err(h, BF_EINVAL, "%llu keys need more than %llu route tiles", (unsigned long long)n,
                        (unsigned long long)tiles);
     if ((uint64_t)nwin > ~0ull / std::max<uint64_t>(window_cap, 1)) return set_err(h, BF_EINVAL, "window_cap overflows");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    hipStream_t s = so.s;
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
+    hipStream_t s = cs.s;
     BfBinPlan plan;
     if (n && !bf_route_plan(n, h->k, nwin, false, d_slot16 != nullptr, &plan))
         return set_err(h, BF_EINVAL, "batch of %llu keys at k=%u over %u windows exceeds one route pass",
@@ -1503,81 +1375,148 @@ int bf_route_chunks_digests_dev(bf_handle* h, const uint32_t* d_digests, uint64_
 }
 
 namespace {
-// side (test only): a key batch [keys, offsets, n) whose SHA-1 words go to side_dig (nullable).
-// d_packed (test only, instead of d_bits): the answers as packed bits in the return trip's layout
-// (window (h, src) at d_packed + (src * nh + h) * ceil(window_cap / 8)).  The sorted test takes
-// ordered chunks and stores them so directly; every other form (the L2 sweep, the direct owner
-// ops, a geometry the ordered form does not take) writes answer bytes into the handle's own
-// buffer and packs them.
-static int shard_chunks_impl(bf_handle* h, const uint32_t* d_recv, uint64_t window_cap, uint32_t nsrc, const uint8_t* d_dir,
-                      uint64_t dir_bytes, uint64_t tiles, const uint64_t* d_counts, uint32_t count_stride,
-                      uint32_t* d_any_new, uint8_t* d_bits, bool test, void* stream,
-                      const uint8_t* side_keys = nullptr, const uint64_t* side_offsets = nullptr, uint64_t side_n = 0,
-                      uint32_t* side_dig = nullptr, uint8_t* d_packed = nullptr) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
-    if (side_n && (!side_keys || !side_offsets || !side_dig)) return set_err(h, BF_EINVAL, "NULL side-hash pointer");
-    if (!nsrc || !window_cap)
-        return side_n ? bf_hash_many_dev(h, side_keys, side_offsets, side_n, side_dig, stream) : BF_OK;
-    if (!d_recv || !d_dir || !d_counts || (test && !d_bits && !d_packed)) return set_err(h, BF_EINVAL, "NULL device pointer");
-    BfChunks cg;
+// ---- the owner ops' bodies.  Each takes its call's scope and opens it (handle_open) after its
+// own refusals, so a composite call runs several of them under the one scope. ----
+
+// The hash-only pass: bf_hash_many_dev, and the side batch of an owner call that has no windows
+// or takes the direct owner ops.
+static int hash_many(CallScope& cs, bf_handle* h, const uint8_t* d_key_bytes, const uint64_t* d_offsets, uint64_t n,
+                     uint32_t* d_digests, void* stream) {
+    if (n && !d_digests) return set_err(h, BF_EINVAL, "d_digests is NULL");
+    if (reinterpret_cast<uintptr_t>(d_digests) & 15u) return set_err(h, BF_EINVAL, "d_digests must be 16-byte aligned");
+    if (n == 0) return BF_OK;
+    if (!d_offsets || !d_key_bytes) return set_err(h, BF_EINVAL, "NULL device pointer");
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
+    uint64_t bias = 0;
+    const uint8_t* k16 = align_keys(d_key_bytes, &bias);
+    BfMarks* mk = prof_begin(h, cs.s);
+    HIPCHK(h, bf_launch_keys(BF_OP_HASH, h->g, k16, d_offsets, bias, n, nullptr,
+                             reinterpret_cast<uint64_t*>(d_digests), nullptr, cs.s));
+    bf_mark(mk, cs.s, "bf_keys_kernel<HASH>");
+    return BF_OK;
+}
+
+// The owner-side op over `count` routed local offsets (uint32 entries when u32 (+ bias), else
+// uint64): the OR into the shard (d_any_new), or with test the answer bytes (d_bits).
+static int shard_op(CallScope& cs, bf_handle* h, bool test, const void* d_local, bool u32, uint64_t bias, uint64_t count,
+                    uint32_t* d_any_new, uint8_t* d_bits, void* stream, const BfWindows& win = BfWindows{}) {
+    if (!test && count && !d_local) return set_err(h, BF_EINVAL, "d_local is NULL");
+    if (test && count && (!d_local || !d_bits)) return set_err(h, BF_EINVAL, "NULL device pointer");
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
+    hipStream_t s = cs.s;
+    // Binned when the routed probes' random line fills clearly exceed a streaming pass over the
+    // shard (binned_pays: the cost model of the whole-filter insert; the test has its own knob,
+    // and no early exit to lose: all k probes of a key arrive).
+    BfBinPlan plan;
+    const uint64_t sub = std::max<uint64_t>(1, bf_binned_max_offsets(h->dev_bytes, h->bin_region_log2));
+    const bool binned = binned_pays(h, test ? h->shard_test_binned_mode : h->binned_mode, (double)count) &&
+                        bf_binned_plan_offsets(h->dev_bytes, std::min(count, sub), h->bin_region_log2, &plan, test) &&
+                        (!win.counts || (win.cap % BF_WINDOW_CAP_ALIGN == 0 && count <= sub));
+    // one binned launch: cn entries at p, the test's answers at d_bits + c0
+    auto launch_binned = [&](const void* p, uint64_t cn, uint64_t c0, const BfWindows& w) -> int {
+        int rc = ensure_scratch(h, plan.scratch_bytes);
+        if (rc) return rc;
+        BfMarks* mk = prof_begin(h, s);
+        if (test)
+            HIPCHK(h, bf_launch_shard_test_binned(h->g, plan, h->dev_bytes, p, u32, cn, h->d_bin_scratch, d_bits + c0, s,
+                                                  mk, bias, w));
+        else
+            HIPCHK(h, bf_launch_shard_insert_binned(h->g, plan, h->dev_bytes, p, u32, cn, h->d_bin_scratch, d_any_new,
+                                                    s, mk, bias, w));
+        return BF_OK;
+    };
+    if (binned && win.counts)   // the windows as one binned pass (entries past a window's count skipped)
+        return launch_binned(d_local, count, 0, win);
+    if (binned) {
+        const size_t esz = u32 ? 4 : 8;
+        for (uint64_t c0 = 0; c0 < count; c0 += sub) {
+            const uint64_t cn = std::min(sub, count - c0);
+            if (cn != std::min(count, sub) && !bf_binned_plan_offsets(h->dev_bytes, cn, h->bin_region_log2, &plan, test))
+                return set_err(h, BF_EINVAL, "binned plan failed for a tail of %llu offsets", (unsigned long long)cn);
+            if (int rc = launch_binned(static_cast<const uint8_t*>(d_local) + c0 * esz, cn, c0, BfWindows{})) return rc;
+        }
+        return BF_OK;
+    }
+    BfMarks* mk = prof_begin(h, s);
+    if (test)
+        HIPCHK(h, bf_launch_shard_test(h->g.bits, h->local_bits, d_local, count, d_bits, u32, s, bias, win));
+    else
+        HIPCHK(h, bf_launch_shard_insert(h->g.bits, h->local_bits, d_local, count, d_any_new, u32, s, bias, h->g.dirty,
+                                         win));
+    bf_mark(mk, s, test ? "shard_test" : "shard_insert");
+    return BF_OK;
+}
+
+// What the hi and the windows forms of the owner ops refuse (the hi forms have no windows).
+static int check_owner_windows(bf_handle* h, uint32_t hi, uint64_t window_cap = 0, uint32_t nwin = 0,
+                               const uint64_t* d_counts = nullptr) {
+    if (((uint64_t)hi << 32) >= h->local_bits) return set_err(h, BF_EINVAL, "hi=%u is past the shard", hi);
+    if (nwin && window_cap && !d_counts) return set_err(h, BF_EINVAL, "d_counts is NULL");
+    if (window_cap && (uint64_t)nwin > ~0ull / window_cap) return set_err(h, BF_EINVAL, "window sizes overflow");
+    if (nwin > 65535) return set_err(h, BF_EINVAL, "at most 65535 windows");
+    return BF_OK;
+}
+
+// One sub-range's windows through the owner op: bf_shard_*_windows_dev, and the chunk ops'
+// direct form.
+static int shard_op_windows(CallScope& cs, bf_handle* h, bool test, const uint32_t* d_local32, uint64_t window_cap,
+                            uint32_t nwin, const uint64_t* d_counts, uint32_t count_stride, uint32_t hi, uint32_t* d_any_new,
+                            uint8_t* d_bits, void* stream) {
+    if (int rc = check_owner_windows(h, hi, window_cap, nwin, d_counts)) return rc;
+    return shard_op(cs, h, test, d_local32, true, (uint64_t)hi << 32, (uint64_t)nwin * window_cap, d_any_new, d_bits,
+                    stream, BfWindows(d_counts, count_stride, nwin, window_cap));
+}
+
+// The owner chunk ops' shared argument checks; on success cg is the geometry (with its tiles),
+// sweep handle_chunks' l2, and ci the call's BfChunkIn but for its recv, dir and counts.
+static int chunk_args(bf_handle* h, uint64_t window_cap, uint32_t nsrc, uint64_t dir_bytes, uint64_t tiles,
+                      uint32_t count_stride, BfChunks* cg, bool* sweep, BfChunkIn* ci) {
     uint32_t nh = 1;
-    bool sweep = false;
-    if (!handle_chunks(h, &cg, &nh, &sweep)) return set_err(h, BF_EINVAL, "this shard count cannot take chunked windows");
-    int rc = check_chunk_args(h, cg, dir_bytes, tiles);
+    if (!handle_chunks(h, cg, &nh, sweep)) return set_err(h, BF_EINVAL, "this shard count cannot take chunked windows");
+    int rc = check_chunk_args(h, *cg, dir_bytes, tiles);
     if (rc) return rc;
     if (count_stride < nh) return set_err(h, BF_EINVAL, "count_stride %u < %u sub-ranges", count_stride, nh);
     const uint64_t total = (uint64_t)nh * nsrc * window_cap;
     if (total / window_cap != (uint64_t)nh * nsrc || total >= (1ull << 32))
         return set_err(h, BF_EINVAL, "%u sub-ranges x %u windows x %llu entries must stay below 2^32", nh, nsrc,
                        (unsigned long long)window_cap);
-    cg.tiles = tiles;
-    BfChunkIn ci;
-    ci.recv = d_recv;
-    ci.dir = d_dir;
-    ci.dir_bytes = dir_bytes;
-    ci.tiles = tiles;
-    ci.cap = window_cap;
-    ci.limit = h->local_bits;
-    ci.counts = reinterpret_cast<const unsigned long long*>(d_counts);
-    ci.cstride = count_stride;
-    ci.nsrc = nsrc;
-    ci.nh = nh;
-    ci.S = cg.S;
-    ci.sup_log2 = cg.sup_log2;
-    BfBinPlan plan;
-    const bool binned = (test ? h->shard_test_binned_mode : h->binned_mode) != 0 &&
-                        bf_chunk_plan(h->dev_bytes, cg, nh, nsrc, window_cap, test, &plan, sweep) &&
-                        ((test ? h->shard_test_binned_mode : h->binned_mode) == 1 ||
-                         (h->dev_bytes >= (64ull << 20) &&
-                          (double)total * 128.0 > kBinnedCostRatio * (double)h->dev_bytes));
-    if (d_packed && binned && !plan.l2test && !side_n &&
-        bf_chunk_plan(h->dev_bytes, cg, nh, nsrc, window_cap, true, &plan, false, true)) {
-        std::lock_guard<std::mutex> lk(h->mu);
-        DeviceGuard dg(h->device);
-        if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-        StreamOrder so(h, pick_stream(h, stream));
-        if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-        if ((rc = ensure_scratch(h, plan.scratch_bytes))) return rc;
-        BfMarks* mk = prof_begin(h, so.s);
-        HIPCHK(h, bf_launch_shard_test_chunks_packed(h->g, plan, h->dev_bytes, ci, h->d_bin_scratch, d_packed, so.s, mk));
-        return BF_OK;
-    }
-    if (d_packed) {   // answer bytes into the handle's buffer, then packed per window
-        const uint64_t nbytes = (uint64_t)nh * nsrc * window_cap;
-        if (nbytes > h->ans8_cap) {
-            std::lock_guard<std::mutex> lk(h->mu);
-            DeviceGuard dg(h->device);
-            if (h->order_valid) HIPCHK(h, hipEventSynchronize(h->order_ev));   // a previous call may still read it
-            if (h->d_ans8) (void)hipFree(h->d_ans8);
-            h->d_ans8 = nullptr;
-            h->ans8_cap = 0;
-            HIPCHK(h, hipMalloc((void**)&h->d_ans8, nbytes));
-            h->ans8_cap = nbytes;
-        }
-        rc = shard_chunks_impl(h, d_recv, window_cap, nsrc, d_dir, dir_bytes, tiles, d_counts, count_stride, nullptr,
-                               h->d_ans8, true, stream, side_keys, side_offsets, side_n, side_dig);
-        if (rc) return rc;
+    cg->tiles = tiles;
+    ci->dir_bytes = dir_bytes;
+    ci->tiles = tiles;
+    ci->cap = window_cap;
+    ci->limit = h->local_bits;
+    ci->cstride = count_stride;
+    ci->nsrc = nsrc;
+    ci->nh = nh;
+    ci->S = cg->S;
+    ci->sup_log2 = cg->sup_log2;
+    return BF_OK;
+}
+
+static void chunk_in(BfChunkIn* ci, const uint32_t* d_recv, const uint8_t* d_dir, const uint64_t* d_counts) {
+    ci->recv = d_recv;
+    ci->dir = d_dir;
+    ci->counts = reinterpret_cast<const unsigned long long*>(d_counts);
+}
+
+// The handle's answer-byte buffer, grown to nbytes.  It runs where it always has, before the
+// test that fills the buffer opens the call: hence its own, unchecked device guard.
+static int ensure_ans8(bf_handle* h, uint64_t nbytes) {
+    if (nbytes <= h->ans8_cap) return BF_OK;
+    DeviceGuard dg(h->device);
+    if (h->order_valid) HIPCHK(h, hipEventSynchronize(h->order_ev));   // a previous call may still read it
+    if (h->d_ans8) (void)hipFree(h->d_ans8);
+    h->d_ans8 = nullptr;
+    h->ans8_cap = 0;
+    HIPCHK(h, hipMalloc((void**)&h->d_ans8, nbytes));
+    h->ans8_cap = nbytes;
+    return BF_OK;
+}
+
+// d_ans8's answer bytes packed per window into d_packed, on the open call's stream.
+static int pack_answers(CallScope& cs, bf_handle* h, uint32_t nh, uint32_t nsrc, uint64_t window_cap, uint8_t* d_packed) {
+    // the table depends on (nsrc, nh, window_cap) only: uploaded (with one sync) when they change
+    if (h->seg_nsrc != nsrc || h->seg_nh != nh || h->seg_wcap != window_cap) {
         std::vector<uint64_t> seg;   // (src, count, dst): sub-range h of source src -> its packed window
         const uint64_t cap8 = (window_cap + 7) / 8;
         for (uint32_t src = 0; src < nsrc; ++src)
@@ -1586,88 +1525,123 @@ static int shard_chunks_impl(bf_handle* h, const uint32_t* d_recv, uint64_t wind
                 seg.push_back(window_cap);
                 seg.push_back(((uint64_t)src * nh + hh) * cap8);
             }
-        std::lock_guard<std::mutex> lk(h->mu);
-        DeviceGuard dg(h->device);
-        if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-        StreamOrder so(h, pick_stream(h, stream));
         const uint64_t sb = seg.size() * 8;
-        // the table depends on (nsrc, nh, window_cap) only: uploaded (with one sync) when they change
-        if (h->seg_nsrc != nsrc || h->seg_nh != nh || h->seg_wcap != window_cap) {
-            if (h->order_valid) HIPCHK(h, hipEventSynchronize(h->order_ev));   // a previous call may still read it
-            HIPCHK(h, hipStreamSynchronize(so.s));
-            if (sb > h->seg_cap) {
-                if (h->d_seg) (void)hipFree(h->d_seg);
-                h->d_seg = nullptr;
-                h->seg_cap = 0;
-                HIPCHK(h, hipMalloc((void**)&h->d_seg, sb));
-                h->seg_cap = sb;
-            }
-            HIPCHK(h, hipMemcpy(h->d_seg, seg.data(), sb, hipMemcpyHostToDevice));
-            h->seg_nsrc = nsrc;
-            h->seg_nh = nh;
-            h->seg_wcap = window_cap;
+        if (h->order_valid) HIPCHK(h, hipEventSynchronize(h->order_ev));   // a previous call may still read it
+        HIPCHK(h, hipStreamSynchronize(cs.s));
+        if (sb > h->seg_cap) {
+            if (h->d_seg) (void)hipFree(h->d_seg);
+            h->d_seg = nullptr;
+            h->seg_cap = 0;
+            HIPCHK(h, hipMalloc((void**)&h->d_seg, sb));
+            h->seg_cap = sb;
         }
-        BfMarks* mk = prof_begin(h, so.s);
-        HIPCHK(h, bf_launch_pack_segments(h->d_ans8, reinterpret_cast<const unsigned long long*>(h->d_seg),
-                                          nh * nsrc, window_cap, d_packed, so.s));
-        bf_mark(mk, so.s, "pack_answers");
+        HIPCHK(h, hipMemcpy(h->d_seg, seg.data(), sb, hipMemcpyHostToDevice));
+        h->seg_nsrc = nsrc;
+        h->seg_nh = nh;
+        h->seg_wcap = window_cap;
+    }
+    BfMarks* mk = prof_begin(h, cs.s);
+    HIPCHK(h, bf_launch_pack_segments(h->d_ans8, reinterpret_cast<const unsigned long long*>(h->d_seg), nh * nsrc,
+                                      window_cap, d_packed, cs.s));
+    bf_mark(mk, cs.s, "pack_answers");
+    return BF_OK;
+}
+
+// The owner op over chunked windows.
+// side (test only): a key batch [keys, offsets, n) whose SHA-1 words go to side_dig (nullable).
+// d_packed (test only, instead of d_bits): the answers as packed bits in the return trip's layout
+// (window (h, src) at d_packed + (src * nh + h) * ceil(window_cap / 8)).  The sorted test takes
+// ordered chunks and stores them so directly; every other form (the L2 sweep, the direct owner
+// ops, a geometry the ordered form does not take) writes answer bytes into the handle's own
+// buffer and packs them.
+static int shard_chunks(CallScope& cs, bf_handle* h, const uint32_t* d_recv, uint64_t window_cap, uint32_t nsrc,
+                        const uint8_t* d_dir, uint64_t dir_bytes, uint64_t tiles, const uint64_t* d_counts,
+                        uint32_t count_stride, uint32_t* d_any_new, uint8_t* d_bits, bool test, void* stream,
+                        const uint8_t* side_keys = nullptr, const uint64_t* side_offsets = nullptr, uint64_t side_n = 0,
+                        uint32_t* side_dig = nullptr, uint8_t* d_packed = nullptr) {
+    if (side_n && (!side_keys || !side_offsets || !side_dig)) return set_err(h, BF_EINVAL, "NULL side-hash pointer");
+    if (!nsrc || !window_cap) return side_n ? hash_many(cs, h, side_keys, side_offsets, side_n, side_dig, stream) : BF_OK;
+    if (!d_recv || !d_dir || !d_counts || (test && !d_bits && !d_packed)) return set_err(h, BF_EINVAL, "NULL device pointer");
+    BfChunks cg;
+    bool sweep = false;
+    BfChunkIn ci;
+    int rc = chunk_args(h, window_cap, nsrc, dir_bytes, tiles, count_stride, &cg, &sweep, &ci);
+    if (rc) return rc;
+    chunk_in(&ci, d_recv, d_dir, d_counts);
+    const uint32_t nh = ci.nh;
+    const uint64_t total = (uint64_t)nh * nsrc * window_cap;
+    BfBinPlan plan, ordered;
+    const bool binned = binned_pays(h, test ? h->shard_test_binned_mode : h->binned_mode, (double)total) &&
+                        bf_chunk_plan(h->dev_bytes, cg, nh, nsrc, window_cap, test, &plan, sweep);
+    if (d_packed && binned && !plan.l2test && !side_n &&
+        bf_chunk_plan(h->dev_bytes, cg, nh, nsrc, window_cap, true, &ordered, false, true)) {
+        if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
+        if ((rc = ensure_scratch(h, ordered.scratch_bytes))) return rc;
+        BfMarks* mk = prof_begin(h, cs.s);
+        HIPCHK(h, bf_launch_shard_test_chunks_packed(h->g, ordered, h->dev_bytes, ci, h->d_bin_scratch, d_packed, cs.s,
+                                                     mk));
         return BF_OK;
+    }
+    if (d_packed) {   // answer bytes into the handle's buffer, packed per window below
+        if ((rc = ensure_ans8(h, total))) return rc;
+        d_bits = h->d_ans8;
     }
     if (!binned) {   // the direct owner ops read the same windows (the directories unused)
         for (uint32_t hi = 0; hi < nh; ++hi) {
-            const uint32_t* rw = d_recv + (uint64_t)hi * nsrc * window_cap;
-            const uint64_t* cw = d_counts + hi;
-            rc = test ? bf_shard_test_windows_dev(h, rw, window_cap, nsrc, cw, count_stride, hi,
-                                                  d_bits + (uint64_t)hi * nsrc * window_cap, stream)
-                      : bf_shard_insert_windows_dev(h, rw, window_cap, nsrc, cw, count_stride, hi, d_any_new, stream);
+            const uint64_t at = (uint64_t)hi * nsrc * window_cap;
+            rc = shard_op_windows(cs, h, test, d_recv + at, window_cap, nsrc, d_counts + hi, count_stride, hi, d_any_new,
+                                  test ? d_bits + at : nullptr, stream);
             if (rc) return rc;
         }
-        return side_n ? bf_hash_many_dev(h, side_keys, side_offsets, side_n, side_dig, stream) : BF_OK;
+        if (side_n && (rc = hash_many(cs, h, side_keys, side_offsets, side_n, side_dig, stream))) return rc;
+    } else {
+        if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
+        hipStream_t s = cs.s;
+        if ((rc = ensure_scratch(h, plan.scratch_bytes))) return rc;
+        BfMarks* mk = prof_begin(h, s);
+        BfSideHash side;
+        if (side_n) {
+            side.keys16 = align_keys(side_keys, &side.bias);
+            side.offsets = side_offsets;
+            side.n = side_n;
+            side.dig = reinterpret_cast<uint4*>(side_dig);
+            side.key_status = h->g.key_status;
+        }
+        if (test)
+            HIPCHK(h, bf_launch_shard_test_chunks(h->g, plan, h->dev_bytes, ci, h->d_bin_scratch, d_bits, s, mk, side));
+        else
+            HIPCHK(h, bf_launch_shard_insert_chunks(h->g, plan, h->dev_bytes, ci, h->d_bin_scratch, d_any_new, s, mk));
     }
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    hipStream_t s = so.s;
-    if ((rc = ensure_scratch(h, plan.scratch_bytes))) return rc;
-    BfMarks* mk = prof_begin(h, s);
-    BfSideHash side;
-    if (side_n) {
-        side.keys16 = align_keys(side_keys, &side.bias);
-        side.offsets = side_offsets;
-        side.n = side_n;
-        side.dig = reinterpret_cast<uint4*>(side_dig);
-        side.key_status = h->g.key_status;
-    }
-    if (test)
-        HIPCHK(h, bf_launch_shard_test_chunks(h->g, plan, h->dev_bytes, ci, h->d_bin_scratch, d_bits, s, mk, side));
-    else
-        HIPCHK(h, bf_launch_shard_insert_chunks(h->g, plan, h->dev_bytes, ci, h->d_bin_scratch, d_any_new, s, mk));
-    return BF_OK;
+    return d_packed ? pack_answers(cs, h, nh, nsrc, window_cap, d_packed) : BF_OK;
 }
 }  // namespace
 
 int bf_shard_insert_chunks_dev(bf_handle* h, const uint32_t* d_recv, uint64_t window_cap, uint32_t nsrc,
                                const uint8_t* d_dir, uint64_t dir_bytes, uint64_t tiles, const uint64_t* d_counts,
                                uint32_t count_stride, uint32_t* d_any_new, void* stream) {
-    return shard_chunks_impl(h, d_recv, window_cap, nsrc, d_dir, dir_bytes, tiles, d_counts, count_stride, d_any_new,
-                             nullptr, false, stream);
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    return shard_chunks(cs, h, d_recv, window_cap, nsrc, d_dir, dir_bytes, tiles, d_counts, count_stride, d_any_new,
+                        nullptr, false, stream);
 }
 
 int bf_shard_test_chunks_dev(bf_handle* h, const uint32_t* d_recv, uint64_t window_cap, uint32_t nsrc,
                              const uint8_t* d_dir, uint64_t dir_bytes, uint64_t tiles, const uint64_t* d_counts,
                              uint32_t count_stride, uint8_t* d_bits, void* stream) {
-    return shard_chunks_impl(h, d_recv, window_cap, nsrc, d_dir, dir_bytes, tiles, d_counts, count_stride, nullptr,
-                             d_bits, true, stream);
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    return shard_chunks(cs, h, d_recv, window_cap, nsrc, d_dir, dir_bytes, tiles, d_counts, count_stride, nullptr, d_bits,
+                        true, stream);
 }
 
 int bf_shard_test_chunks_packed_dev(bf_handle* h, const uint32_t* d_recv, uint64_t window_cap, uint32_t nsrc,
                                     const uint8_t* d_dir, uint64_t dir_bytes, uint64_t tiles, const uint64_t* d_counts,
                                     uint32_t count_stride, uint8_t* d_packed, void* stream) {
-    if (h && !h->multi && !d_packed) return set_err(h, BF_EINVAL, "d_packed is NULL");
-    return shard_chunks_impl(h, d_recv, window_cap, nsrc, d_dir, dir_bytes, tiles, d_counts, count_stride, nullptr,
-                             nullptr, true, stream, nullptr, nullptr, 0, nullptr, d_packed);
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    if (!d_packed) return set_err(h, BF_EINVAL, "d_packed is NULL");
+    return shard_chunks(cs, h, d_recv, window_cap, nsrc, d_dir, dir_bytes, tiles, d_counts, count_stride, nullptr, nullptr,
+                        true, stream, nullptr, nullptr, 0, nullptr, d_packed);
 }
 
 int bf_shard_insert_test_chunks_packed_dev(bf_handle* h, const uint32_t* d_ins_recv, const uint8_t* d_ins_dir,
@@ -1677,68 +1651,43 @@ int bf_shard_insert_test_chunks_packed_dev(bf_handle* h, const uint32_t* d_ins_r
                                            uint32_t count_stride, uint32_t* d_any_new, uint8_t* d_packed,
                                            const uint8_t* d_next_keys, const uint64_t* d_next_offsets,
                                            uint64_t n_next, uint32_t* d_next_digests, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
     if (!d_packed) return set_err(h, BF_EINVAL, "d_packed is NULL");
     if (n_next && (!d_next_keys || !d_next_offsets || !d_next_digests))
         return set_err(h, BF_EINVAL, "NULL side-hash pointer");
     if (n_next && (reinterpret_cast<uintptr_t>(d_next_digests) & 15u))
         return set_err(h, BF_EINVAL, "d_next_digests must be 16-byte aligned");
     if (!nsrc || !window_cap)
-        return n_next ? bf_hash_many_dev(h, d_next_keys, d_next_offsets, n_next, d_next_digests, stream) : BF_OK;
+        return n_next ? hash_many(cs, h, d_next_keys, d_next_offsets, n_next, d_next_digests, stream) : BF_OK;
     if (!d_ins_recv || !d_ins_dir || !d_ins_counts || !d_tst_recv || !d_tst_dir || !d_tst_counts)
         return set_err(h, BF_EINVAL, "NULL device pointer");
     BfChunks cg;
-    uint32_t nh = 1;
     bool sweep = false;
-    if (!handle_chunks(h, &cg, &nh, &sweep)) return set_err(h, BF_EINVAL, "this shard count cannot take chunked windows");
-    int rc = check_chunk_args(h, cg, dir_bytes, tiles);
+    BfChunkIn ci;
+    int rc = chunk_args(h, window_cap, nsrc, dir_bytes, tiles, count_stride, &cg, &sweep, &ci);
     if (rc) return rc;
-    if (count_stride < nh) return set_err(h, BF_EINVAL, "count_stride %u < %u sub-ranges", count_stride, nh);
-    const uint64_t total = (uint64_t)nh * nsrc * window_cap;
-    if (total / window_cap != (uint64_t)nh * nsrc || total >= (1ull << 32))
-        return set_err(h, BF_EINVAL, "%u sub-ranges x %u windows x %llu entries must stay below 2^32", nh, nsrc,
-                       (unsigned long long)window_cap);
-    cg.tiles = tiles;
+    const double total = (double)((uint64_t)ci.nh * nsrc * window_cap);
     BfBinPlan pi, pt;
     // one pass only where both owner ops would take their sorted binned forms on this shard (the
-    // same rule as shard_chunks_impl) and the include? its ordered form; else the two calls
-    const bool dense_enough = h->dev_bytes >= (64ull << 20) && (double)total * 128.0 > kBinnedCostRatio * (double)h->dev_bytes;
-    const bool fused = h->binned_mode != 0 && h->shard_test_binned_mode != 0 && !sweep &&
-                       (h->binned_mode == 1 || dense_enough) && (h->shard_test_binned_mode == 1 || dense_enough) &&
-                       bf_chunk_plan(h->dev_bytes, cg, nh, nsrc, window_cap, false, &pi) &&
-                       bf_chunk_plan(h->dev_bytes, cg, nh, nsrc, window_cap, true, &pt, false, true);
+    // same rule as shard_chunks) and the include? its ordered form; else the two ops and the
+    // hash, one after the other under this call's scope
+    const bool fused = binned_pays(h, h->binned_mode, total) && binned_pays(h, h->shard_test_binned_mode, total) &&
+                       !sweep && bf_chunk_plan(h->dev_bytes, cg, ci.nh, nsrc, window_cap, false, &pi) &&
+                       bf_chunk_plan(h->dev_bytes, cg, ci.nh, nsrc, window_cap, true, &pt, false, true);
     if (!fused) {
-        rc = bf_shard_insert_chunks_dev(h, d_ins_recv, window_cap, nsrc, d_ins_dir, dir_bytes, tiles, d_ins_counts,
-                                        count_stride, d_any_new, stream);
+        rc = shard_chunks(cs, h, d_ins_recv, window_cap, nsrc, d_ins_dir, dir_bytes, tiles, d_ins_counts, count_stride,
+                          d_any_new, nullptr, false, stream);
         if (rc) return rc;
-        rc = bf_shard_test_chunks_packed_dev(h, d_tst_recv, window_cap, nsrc, d_tst_dir, dir_bytes, tiles, d_tst_counts,
-                                             count_stride, d_packed, stream);
+        rc = shard_chunks(cs, h, d_tst_recv, window_cap, nsrc, d_tst_dir, dir_bytes, tiles, d_tst_counts, count_stride,
+                          nullptr, nullptr, true, stream, nullptr, nullptr, 0, nullptr, d_packed);
         if (rc) return rc;
-        return n_next ? bf_hash_many_dev(h, d_next_keys, d_next_offsets, n_next, d_next_digests, stream) : BF_OK;
+        return n_next ? hash_many(cs, h, d_next_keys, d_next_offsets, n_next, d_next_digests, stream) : BF_OK;
     }
-    BfChunkIn cii;
-    cii.recv = d_ins_recv;
-    cii.dir = d_ins_dir;
-    cii.dir_bytes = dir_bytes;
-    cii.tiles = tiles;
-    cii.cap = window_cap;
-    cii.limit = h->local_bits;
-    cii.counts = reinterpret_cast<const unsigned long long*>(d_ins_counts);
-    cii.cstride = count_stride;
-    cii.nsrc = nsrc;
-    cii.nh = nh;
-    cii.S = cg.S;
-    cii.sup_log2 = cg.sup_log2;
-    BfChunkIn cit = cii;
-    cit.recv = d_tst_recv;
-    cit.dir = d_tst_dir;
-    cit.counts = reinterpret_cast<const unsigned long long*>(d_tst_counts);
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
+    BfChunkIn cii = ci, cit = ci;
+    chunk_in(&cii, d_ins_recv, d_ins_dir, d_ins_counts);
+    chunk_in(&cit, d_tst_recv, d_tst_dir, d_tst_counts);
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
     if ((rc = ensure_scratch(h, bf_chunk_scratch_bytes(pi) + bf_chunk_scratch_bytes(pt)))) return rc;
     BfSideHash side;
     if (n_next) {
@@ -1748,9 +1697,9 @@ int bf_shard_insert_test_chunks_packed_dev(bf_handle* h, const uint32_t* d_ins_r
         side.dig = reinterpret_cast<uint4*>(d_next_digests);
         side.key_status = h->g.key_status;
     }
-    BfMarks* mk = prof_begin(h, so.s);
+    BfMarks* mk = prof_begin(h, cs.s);
     HIPCHK(h, bf_launch_shard_insert_test_chunks_packed(h->g, pi, pt, h->dev_bytes, cii, cit, h->d_bin_scratch,
-                                                        d_any_new, d_packed, so.s, mk, side));
+                                                        d_any_new, d_packed, cs.s, mk, side));
     return BF_OK;
 }
 
@@ -1759,15 +1708,17 @@ int bf_shard_test_chunks_hash_dev(bf_handle* h, const uint32_t* d_recv, uint64_t
                                   uint32_t count_stride, uint8_t* d_bits, const uint8_t* d_next_keys,
                                   const uint64_t* d_next_offsets, uint64_t n_next, uint32_t* d_next_digests,
                                   void* stream) {
-    return shard_chunks_impl(h, d_recv, window_cap, nsrc, d_dir, dir_bytes, tiles, d_counts, count_stride, nullptr,
-                             d_bits, true, stream, d_next_keys, d_next_offsets, n_next, d_next_digests);
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    return shard_chunks(cs, h, d_recv, window_cap, nsrc, d_dir, dir_bytes, tiles, d_counts, count_stride, nullptr, d_bits,
+                        true, stream, d_next_keys, d_next_offsets, n_next, d_next_digests);
 }
 
 int bf_combine_chunks_packed_dev(bf_handle* h, const uint8_t* d_packed, const uint16_t* d_slot16, uint64_t window_cap,
                                  const uint8_t* d_dir, uint64_t dir_bytes, uint64_t tiles, const uint64_t* d_counts,
                                  uint64_t n, uint8_t* d_out, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
     if (n && (!d_packed || !d_slot16 || !d_dir || !d_counts || !d_out))
         return set_err(h, BF_EINVAL, "NULL device pointer");
     BfChunks cg;
@@ -1780,12 +1731,8 @@ int bf_combine_chunks_packed_dev(bf_handle* h, const uint8_t* d_packed, const ui
     cg.dir = const_cast<uint8_t*>(d_dir);
     cg.dir_bytes = dir_bytes;
     cg.tiles = tiles;
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    hipStream_t s = so.s;
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
+    hipStream_t s = cs.s;
     BfMarks* mk = prof_begin(h, s);
     HIPCHK(h, bf_launch_combine_chunks_packed(d_packed, d_slot16, window_cap, cg, h->shards * nh,
                                               reinterpret_cast<const unsigned long long*>(d_counts), n, (uint32_t)tk,
@@ -1794,176 +1741,59 @@ int bf_combine_chunks_packed_dev(bf_handle* h, const uint8_t* d_packed, const ui
     return BF_OK;
 }
 
-namespace {
-// Owner-side OR of `count` routed local offsets: uint32 entries when u32 (+ bias), else uint64.
-static int shard_insert_impl(bf_handle* h, const void* d_local, bool u32, uint64_t bias, uint64_t count, uint32_t* d_any_new,
-                      void* stream, const BfWindows& win = BfWindows{}) {
-    if (!h) return BF_EINVAL;
-    if (count && !d_local) return set_err(h, BF_EINVAL, "d_local is NULL");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    hipStream_t s = so.s;
-    // Binned when the routed probes' random line fills clearly exceed a streaming pass
-    // over the shard (same policy and knob as the whole-filter insert).
-    BfBinPlan plan;
-    const uint64_t sub = std::max<uint64_t>(1, bf_binned_max_offsets(h->dev_bytes, h->bin_region_log2));
-    const bool binned = h->binned_mode != 0 &&
-                        bf_binned_plan_offsets(h->dev_bytes, std::min(count, sub), h->bin_region_log2, &plan) &&
-                        (h->binned_mode == 1 || (h->dev_bytes >= (64ull << 20) &&
-                                                 (double)count * 128.0 > kBinnedCostRatio * (double)h->dev_bytes)) &&
-                        (!win.counts || (win.cap % BF_WINDOW_CAP_ALIGN == 0 && count <= sub));
-    if (binned && win.counts) {   // the windows as one binned pass (entries past a window's count skipped)
-        int rc = ensure_scratch(h, plan.scratch_bytes);
-        if (rc) return rc;
-        BfMarks* mk = prof_begin(h, s);
-        HIPCHK(h, bf_launch_shard_insert_binned(h->g, plan, h->dev_bytes, d_local, u32, count, h->d_bin_scratch,
-                                                d_any_new, s, mk, bias, win));
-        return BF_OK;
-    }
-    if (binned) {
-        const size_t esz = u32 ? 4 : 8;
-        for (uint64_t c0 = 0; c0 < count; c0 += sub) {
-            const uint64_t cn = std::min(sub, count - c0);
-            if (cn != std::min(count, sub) && !bf_binned_plan_offsets(h->dev_bytes, cn, h->bin_region_log2, &plan))
-                return set_err(h, BF_EINVAL, "binned plan failed for a tail of %llu offsets", (unsigned long long)cn);
-            int rc = ensure_scratch(h, plan.scratch_bytes);
-            if (rc) return rc;
-            BfMarks* mk = prof_begin(h, s);
-            HIPCHK(h, bf_launch_shard_insert_binned(h->g, plan, h->dev_bytes,
-                                                    static_cast<const uint8_t*>(d_local) + c0 * esz, u32, cn,
-                                                    h->d_bin_scratch, d_any_new, s, mk, bias));
-        }
-        return BF_OK;
-    }
-    BfMarks* mk = prof_begin(h, s);
-    HIPCHK(h, bf_launch_shard_insert(h->g.bits, h->local_bits, d_local, count, d_any_new, u32, s, bias, h->g.dirty, win));
-    bf_mark(mk, s, "shard_insert");
-    return BF_OK;
-}
-}  // namespace
-
 int bf_shard_insert_dev(bf_handle* h, const void* d_local, uint64_t count, uint32_t* d_any_new, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
-    return shard_insert_impl(h, d_local, h->route32, 0, count, d_any_new, stream);
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    return shard_op(cs, h, false, d_local, h->route32, 0, count, d_any_new, nullptr, stream);
 }
 
 int bf_shard_insert_hi_dev(bf_handle* h, const uint32_t* d_local32, uint64_t count, uint32_t hi, uint32_t* d_any_new,
                            void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
-    if (((uint64_t)hi << 32) >= h->local_bits) return set_err(h, BF_EINVAL, "hi=%u is past the shard", hi);
-    return shard_insert_impl(h, d_local32, true, (uint64_t)hi << 32, count, d_any_new, stream);
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    if (int rc = check_owner_windows(h, hi)) return rc;
+    return shard_op(cs, h, false, d_local32, true, (uint64_t)hi << 32, count, d_any_new, nullptr, stream);
 }
-
-namespace {
-static int shard_test_impl(bf_handle* h, const void* d_local, bool u32, uint64_t bias, uint64_t count, uint8_t* d_bits,
-                    void* stream, const BfWindows& win = BfWindows{}) {
-    if (!h) return BF_EINVAL;
-    if (count && (!d_local || !d_bits)) return set_err(h, BF_EINVAL, "NULL device pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    hipStream_t s = so.s;
-    // Binned like the shard insert: routed probes carry no early exit (all k arrive), so
-    // one streaming pass over the shard beats a random line fill per probe once the
-    // probes outnumber the shard's lines (same cost model and knob shape as the insert).
-    BfBinPlan plan;
-    const uint64_t sub = std::max<uint64_t>(1, bf_binned_max_offsets(h->dev_bytes, h->bin_region_log2));
-    const uint32_t mode = h->shard_test_binned_mode;
-    const bool binned = mode != 0 &&
-                        bf_binned_plan_offsets(h->dev_bytes, std::min(count, sub), h->bin_region_log2, &plan, true) &&
-                        (mode == 1 || (h->dev_bytes >= (64ull << 20) &&
-                                       (double)count * 128.0 > kBinnedCostRatio * (double)h->dev_bytes)) &&
-                        (!win.counts || (win.cap % BF_WINDOW_CAP_ALIGN == 0 && count <= sub));
-    if (binned && win.counts) {
-        int rc = ensure_scratch(h, plan.scratch_bytes);
-        if (rc) return rc;
-        BfMarks* mk = prof_begin(h, s);
-        HIPCHK(h, bf_launch_shard_test_binned(h->g, plan, h->dev_bytes, d_local, u32, count, h->d_bin_scratch, d_bits,
-                                              s, mk, bias, win));
-        return BF_OK;
-    }
-    if (binned) {
-        const size_t esz = u32 ? 4 : 8;
-        for (uint64_t c0 = 0; c0 < count; c0 += sub) {
-            const uint64_t cn = std::min(sub, count - c0);
-            if (cn != std::min(count, sub) &&
-                !bf_binned_plan_offsets(h->dev_bytes, cn, h->bin_region_log2, &plan, true))
-                return set_err(h, BF_EINVAL, "binned plan failed for a tail of %llu offsets", (unsigned long long)cn);
-            int rc = ensure_scratch(h, plan.scratch_bytes);
-            if (rc) return rc;
-            BfMarks* mk = prof_begin(h, s);
-            HIPCHK(h, bf_launch_shard_test_binned(h->g, plan, h->dev_bytes,
-                                                  static_cast<const uint8_t*>(d_local) + c0 * esz, u32, cn,
-                                                  h->d_bin_scratch, d_bits + c0, s, mk, bias));
-        }
-        return BF_OK;
-    }
-    BfMarks* mk = prof_begin(h, s);
-    HIPCHK(h, bf_launch_shard_test(h->g.bits, h->local_bits, d_local, count, d_bits, u32, s, bias, win));
-    bf_mark(mk, s, "shard_test");
-    return BF_OK;
-}
-
-}  // namespace
 
 int bf_shard_insert_windows_dev(bf_handle* h, const uint32_t* d_local32, uint64_t window_cap, uint32_t nwin,
                                 const uint64_t* d_counts, uint32_t count_stride, uint32_t hi, uint32_t* d_any_new,
                                 void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
-    if (((uint64_t)hi << 32) >= h->local_bits) return set_err(h, BF_EINVAL, "hi=%u is past the shard", hi);
-    if (nwin && window_cap && !d_counts) return set_err(h, BF_EINVAL, "d_counts is NULL");
-    if (window_cap && (uint64_t)nwin > ~0ull / window_cap) return set_err(h, BF_EINVAL, "window sizes overflow");
-    if (nwin > 65535) return set_err(h, BF_EINVAL, "at most 65535 windows");
-    return shard_insert_impl(h, d_local32, true, (uint64_t)hi << 32, (uint64_t)nwin * window_cap, d_any_new, stream,
-                             BfWindows(d_counts, count_stride, nwin, window_cap));
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    return shard_op_windows(cs, h, false, d_local32, window_cap, nwin, d_counts, count_stride, hi, d_any_new, nullptr,
+                            stream);
 }
 
 int bf_shard_test_windows_dev(bf_handle* h, const uint32_t* d_local32, uint64_t window_cap, uint32_t nwin,
                               const uint64_t* d_counts, uint32_t count_stride, uint32_t hi, uint8_t* d_bits,
                               void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
-    if (((uint64_t)hi << 32) >= h->local_bits) return set_err(h, BF_EINVAL, "hi=%u is past the shard", hi);
-    if (nwin && window_cap && !d_counts) return set_err(h, BF_EINVAL, "d_counts is NULL");
-    if (window_cap && (uint64_t)nwin > ~0ull / window_cap) return set_err(h, BF_EINVAL, "window sizes overflow");
-    if (nwin > 65535) return set_err(h, BF_EINVAL, "at most 65535 windows");
-    return shard_test_impl(h, d_local32, true, (uint64_t)hi << 32, (uint64_t)nwin * window_cap, d_bits, stream,
-                           BfWindows(d_counts, count_stride, nwin, window_cap));
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    return shard_op_windows(cs, h, true, d_local32, window_cap, nwin, d_counts, count_stride, hi, nullptr, d_bits,
+                            stream);
 }
 
 int bf_shard_test_dev(bf_handle* h, const void* d_local, uint64_t count, uint8_t* d_bits, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
-    return shard_test_impl(h, d_local, h->route32, 0, count, d_bits, stream);
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    return shard_op(cs, h, true, d_local, h->route32, 0, count, nullptr, d_bits, stream);
 }
 
 int bf_shard_test_hi_dev(bf_handle* h, const uint32_t* d_local32, uint64_t count, uint32_t hi, uint8_t* d_bits,
                          void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
-    if (((uint64_t)hi << 32) >= h->local_bits) return set_err(h, BF_EINVAL, "hi=%u is past the shard", hi);
-    return shard_test_impl(h, d_local32, true, (uint64_t)hi << 32, count, d_bits, stream);
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    if (int rc = check_owner_windows(h, hi)) return rc;
+    return shard_op(cs, h, true, d_local32, true, (uint64_t)hi << 32, count, nullptr, d_bits, stream);
 }
 
 int bf_combine_dev(bf_handle* h, const uint8_t* d_bits, const uint32_t* d_slot, uint64_t n, uint8_t* d_out,
                    void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
     if (n && (!d_bits || !d_slot || !d_out)) return set_err(h, BF_EINVAL, "NULL device pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    hipStream_t s = so.s;
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
+    hipStream_t s = cs.s;
     BfMarks* mk = prof_begin(h, s);
     HIPCHK(h, bf_launch_combine(d_bits, d_slot, n, h->k, d_out, s));
     bf_mark(mk, s, "combine");
@@ -1972,15 +1802,11 @@ int bf_combine_dev(bf_handle* h, const uint8_t* d_bits, const uint32_t* d_slot, 
 
 int bf_combine_windows_dev(bf_handle* h, const uint8_t* d_bits, const uint32_t* d_slot, uint64_t window_cap,
                            uint32_t nwin, const uint64_t* d_counts, uint64_t n, uint8_t* d_out, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
     if (n && (!d_bits || !d_slot || !d_counts || !d_out)) return set_err(h, BF_EINVAL, "NULL device pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    hipStream_t s = so.s;
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
+    hipStream_t s = cs.s;
     BfMarks* mk = prof_begin(h, s);
     HIPCHK(h, bf_launch_combine_windows(d_bits, d_slot, window_cap, reinterpret_cast<const unsigned long long*>(d_counts),
                                         nwin, n, d_out, s));
@@ -1990,16 +1816,12 @@ int bf_combine_windows_dev(bf_handle* h, const uint8_t* d_bits, const uint32_t* 
 
 int bf_pack_segments_dev(bf_handle* h, const uint8_t* d_bits, const uint64_t* d_seg, uint32_t nseg,
                          uint64_t max_count, uint8_t* d_packed, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
     if (nseg && (!d_bits || !d_seg || !d_packed)) return set_err(h, BF_EINVAL, "NULL device pointer");
     if (nseg > 65535) return set_err(h, BF_EINVAL, "at most 65535 segments");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    hipStream_t s = so.s;
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
+    hipStream_t s = cs.s;
     BfMarks* mk = prof_begin(h, s);
     HIPCHK(h, bf_launch_pack_segments(d_bits, reinterpret_cast<const unsigned long long*>(d_seg), nseg, max_count,
                                       d_packed, s));
@@ -2009,15 +1831,11 @@ int bf_pack_segments_dev(bf_handle* h, const uint8_t* d_bits, const uint64_t* d_
 
 int bf_combine_windows_packed_dev(bf_handle* h, const uint8_t* d_packed, const uint32_t* d_slot, uint64_t window_cap,
                                   uint32_t nwin, const uint64_t* d_counts, uint64_t n, uint8_t* d_out, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
     if (n && (!d_packed || !d_slot || !d_counts || !d_out)) return set_err(h, BF_EINVAL, "NULL device pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    hipStream_t s = so.s;
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
+    hipStream_t s = cs.s;
     BfMarks* mk = prof_begin(h, s);
     HIPCHK(h, bf_launch_combine_windows_packed(d_packed, d_slot, window_cap,
                                                reinterpret_cast<const unsigned long long*>(d_counts), nwin, n, d_out,
@@ -2028,40 +1846,31 @@ int bf_combine_windows_packed_dev(bf_handle* h, const uint8_t* d_packed, const u
 
 int bf_insert_many_dev(bf_handle* h, const uint8_t* d_key_bytes, const uint64_t* d_offsets, uint64_t n,
                        uint32_t* d_any_new, uint8_t* d_per_key_new, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
     const BfOp op = (d_any_new || d_per_key_new) ? BF_OP_INSERT_FLAGS : BF_OP_INSERT;
     return run_dev(h, op, d_key_bytes, d_offsets, n, d_per_key_new, nullptr, d_any_new, stream);
 }
 
 int bf_include_many_dev(bf_handle* h, const uint8_t* d_key_bytes, const uint64_t* d_offsets, uint64_t n,
                         uint8_t* d_out, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
     return run_dev(h, BF_OP_INCLUDE, d_key_bytes, d_offsets, n, d_out, nullptr, nullptr, stream);
 }
 
 int bf_indexes_many_dev(bf_handle* h, const uint8_t* d_key_bytes, const uint64_t* d_offsets, uint64_t n,
                         uint64_t* d_out, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
     return run_dev(h, BF_OP_INDEXES, d_key_bytes, d_offsets, n, nullptr, d_out, nullptr, stream);
 }
 
 namespace {
 // The digest ops: binned insert when it pays (as for keys), else one direct lane per digest.
-static int run_digests(bf_handle* h, BfOp op, const uint32_t* d_dig, uint64_t n, uint8_t* d_out8, uint32_t* d_flag,
-                void* stream) {
-    if (!h) return BF_EINVAL;
-    if (h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
+static int run_digests(CallScope& cs, bf_handle* h, BfOp op, const uint32_t* d_dig, uint64_t n, uint8_t* d_out8,
+                       uint32_t* d_flag, void* stream) {
     if (n == 0) return BF_OK;
     if (!d_dig) return set_err(h, BF_EINVAL, "d_digests is NULL");
     if (reinterpret_cast<uintptr_t>(d_dig) & 15u) return set_err(h, BF_EINVAL, "d_digests must be 16-byte aligned");
     if (op == BF_OP_INCLUDE && !d_out8) return set_err(h, BF_EINVAL, "d_out is NULL");
     if (h->shards > 1) return set_err(h, BF_EINVAL, "handle holds one shard of a partitioned filter");
     if (h->engine != BF_ENGINE_RUBY) return set_err(h, BF_EINVAL, "digests carry the ruby driver's derivation only");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
     const uint4* dig = reinterpret_cast<const uint4*>(d_dig);
     const bool is_insert = op == BF_OP_INSERT || op == BF_OP_INSERT_FLAGS;
     BfBinPlan plan;
@@ -2073,56 +1882,45 @@ static int run_digests(bf_handle* h, BfOp op, const uint32_t* d_dig, uint64_t n,
                 return set_err(h, BF_EINVAL, "binned plan failed for a tail of %llu keys", (unsigned long long)cn);
             int rc = ensure_scratch(h, plan.scratch_bytes);
             if (rc) return rc;
-            BfMarks* mk = prof_begin(h, so.s);
+            BfMarks* mk = prof_begin(h, cs.s);
             HIPCHK(h, bf_launch_insert_binned_digests(h->g, plan, h->dev_bytes, dig + c0, cn, h->d_bin_scratch,
-                                                      op == BF_OP_INSERT_FLAGS ? d_flag : nullptr, so.s, mk));
+                                                      op == BF_OP_INSERT_FLAGS ? d_flag : nullptr, cs.s, mk));
         }
         return BF_OK;
     }
-    BfMarks* mk = prof_begin(h, so.s);
-    HIPCHK(h, bf_launch_digests(op, h->g, dig, n, d_out8, nullptr, d_flag, so.s));
-    bf_mark(mk, so.s, op == BF_OP_INCLUDE ? "digest_kernel<INCLUDE>" : "digest_kernel<INSERT>");
+    BfMarks* mk = prof_begin(h, cs.s);
+    HIPCHK(h, bf_launch_digests(op, h->g, dig, n, d_out8, nullptr, d_flag, cs.s));
+    bf_mark(mk, cs.s, op == BF_OP_INCLUDE ? "digest_kernel<INCLUDE>" : "digest_kernel<INSERT>");
     return BF_OK;
 }
 }  // namespace
 
 int bf_hash_many_dev(bf_handle* h, const uint8_t* d_key_bytes, const uint64_t* d_offsets, uint64_t n,
                      uint32_t* d_digests, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
-    if (n && !d_digests) return set_err(h, BF_EINVAL, "d_digests is NULL");
-    if (reinterpret_cast<uintptr_t>(d_digests) & 15u) return set_err(h, BF_EINVAL, "d_digests must be 16-byte aligned");
-    if (n == 0) return BF_OK;
-    if (!d_offsets || !d_key_bytes) return set_err(h, BF_EINVAL, "NULL device pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    uint64_t bias = 0;
-    const uint8_t* k16 = align_keys(d_key_bytes, &bias);
-    BfMarks* mk = prof_begin(h, so.s);
-    HIPCHK(h, bf_launch_keys(BF_OP_HASH, h->g, k16, d_offsets, bias, n, nullptr,
-                             reinterpret_cast<uint64_t*>(d_digests), nullptr, so.s));
-    bf_mark(mk, so.s, "bf_keys_kernel<HASH>");
-    return BF_OK;
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    return hash_many(cs, h, d_key_bytes, d_offsets, n, d_digests, stream);
 }
 
 int bf_insert_digests_dev(bf_handle* h, const uint32_t* d_digests, uint64_t n, uint32_t* d_any_new,
                           uint8_t* d_per_key_new, void* stream) {
-    if (h && !h->multi && d_per_key_new) return set_err(h, BF_EINVAL, "per_key_new needs the keys (bf_insert_many_dev)");
-    return run_digests(h, d_any_new ? BF_OP_INSERT_FLAGS : BF_OP_INSERT, d_digests, n, nullptr, d_any_new, stream);
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    if (d_per_key_new) return set_err(h, BF_EINVAL, "per_key_new needs the keys (bf_insert_many_dev)");
+    return run_digests(cs, h, d_any_new ? BF_OP_INSERT_FLAGS : BF_OP_INSERT, d_digests, n, nullptr, d_any_new, stream);
 }
 
 int bf_include_digests_dev(bf_handle* h, const uint32_t* d_digests, uint64_t n, uint8_t* d_out, void* stream) {
-    return run_digests(h, BF_OP_INCLUDE, d_digests, n, d_out, nullptr, stream);
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    return run_digests(cs, h, BF_OP_INCLUDE, d_digests, n, d_out, nullptr, stream);
 }
 
 int bf_include_hash_dev(bf_handle* h, const uint8_t* d_key_bytes, const uint64_t* d_offsets, uint64_t n,
                         uint8_t* d_out, const uint8_t* d_next_key_bytes, const uint64_t* d_next_offsets,
                         uint64_t n_next, uint32_t* d_next_digests, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
     if (n && (!d_key_bytes || !d_offsets || !d_out)) return set_err(h, BF_EINVAL, "NULL device pointer");
     if (n_next && (!d_next_key_bytes || !d_next_offsets || !d_next_digests))
         return set_err(h, BF_EINVAL, "NULL device pointer (next batch)");
@@ -2131,18 +1929,14 @@ int bf_include_hash_dev(bf_handle* h, const uint8_t* d_key_bytes, const uint64_t
     if (h->shards > 1) return set_err(h, BF_EINVAL, "handle holds one shard of a partitioned filter");
     if (h->engine != BF_ENGINE_RUBY) return set_err(h, BF_EINVAL, "digests carry the ruby driver's derivation only");
     if (n + n_next == 0) return BF_OK;
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
     uint64_t bias = 0, nbias = 0;
     const uint8_t* k16 = n ? align_keys(d_key_bytes, &bias) : nullptr;
     const uint8_t* nk16 = n_next ? align_keys(d_next_key_bytes, &nbias) : nullptr;
-    BfMarks* mk = prof_begin(h, so.s);
+    BfMarks* mk = prof_begin(h, cs.s);
     HIPCHK(h, bf_launch_include_hash(h->g, k16, d_offsets, bias, n, d_out, nk16, d_next_offsets, nbias, n_next,
-                                     reinterpret_cast<uint4*>(d_next_digests), so.s));
-    bf_mark(mk, so.s, "include_hash_kernel");
+                                     reinterpret_cast<uint4*>(d_next_digests), cs.s));
+    bf_mark(mk, cs.s, "include_hash_kernel");
     return BF_OK;
 }
 
@@ -2171,10 +1965,8 @@ int bf_region_sets_capacity(const bf_handle* h, uint64_t n, uint64_t* bytes) {
 }
 
 namespace {
-int encode_sets(bf_handle* h, const uint8_t* d_keys, const uint64_t* d_offsets, uint64_t n, bool dig,
+int encode_sets(CallScope& cs, bf_handle* h, const uint8_t* d_keys, const uint64_t* d_offsets, uint64_t n, bool dig,
                 uint32_t* d_sets, uint64_t sets_bytes, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
     if (!d_sets || (reinterpret_cast<uintptr_t>(d_sets) & 15u)) return set_err(h, BF_EINVAL, "d_sets must be 16-byte aligned");
     if (n && (!d_keys || (!dig && !d_offsets))) return set_err(h, BF_EINVAL, "NULL device pointer");
     if (dig && n && (reinterpret_cast<uintptr_t>(d_keys) & 15u)) return set_err(h, BF_EINVAL, "d_digests must be 16-byte aligned");
@@ -2194,18 +1986,14 @@ int encode_sets(bf_handle* h, const uint8_t* d_keys, const uint64_t* d_offsets, 
         return set_err(h, BF_EINVAL, "a batch of %llu keys does not sort in one pass (at most %llu keys per set buffer)",
                        (unsigned long long)n,
                        (unsigned long long)bf_binned_max_keys(h->k, h->dev_bytes, h->bin_region_log2));
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h, false)) return krc;   // (an encoder handle encodes: no bitset read)
+    if (int krc = handle_open(cs, h, pick_stream(h, stream), false)) return krc;
     if (n) {
         int rc = ensure_scratch(h, plan.scratch_bytes);
         if (rc) return rc;
     }
     uint64_t bias = 0;
     const uint8_t* k16 = (n && !dig) ? align_keys(d_keys, &bias) : d_keys;
-    BfMarks* mk = n ? prof_begin(h, so.s) : nullptr;
+    BfMarks* mk = n ? prof_begin(h, cs.s) : nullptr;
     // an encoder handle encodes beside another stream's apply: a persistent encode on 3/4 of the
     // CUs (bf_binned.hip sets_encode_persistent_kernel)
     uint32_t pgrid = 0;
@@ -2216,25 +2004,29 @@ int encode_sets(bf_handle* h, const uint8_t* d_keys, const uint64_t* d_offsets, 
         pgrid = std::max<uint32_t>(1u, (uint32_t)cus * 3u / 4u);
     }
     HIPCHK(h, bf_launch_encode_sets(h->g, plan, h->dev_bytes, k16, d_offsets, bias, n, dig, h->d_bin_scratch, d_sets,
-                                    std::min<uint64_t>(sets_bytes / 4, 0xFFFFFFFFull), so.s, mk, pgrid));
+                                    std::min<uint64_t>(sets_bytes / 4, 0xFFFFFFFFull), cs.s, mk, pgrid));
     return BF_OK;
 }
 }  // namespace
 
 int bf_encode_region_sets_dev(bf_handle* h, const uint8_t* d_key_bytes, const uint64_t* d_offsets, uint64_t n,
                               uint32_t* d_sets, uint64_t sets_bytes, void* stream) {
-    return encode_sets(h, d_key_bytes, d_offsets, n, false, d_sets, sets_bytes, stream);
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    return encode_sets(cs, h, d_key_bytes, d_offsets, n, false, d_sets, sets_bytes, stream);
 }
 
 int bf_encode_region_sets_digests_dev(bf_handle* h, const uint32_t* d_digests, uint64_t n, uint32_t* d_sets,
                                       uint64_t sets_bytes, void* stream) {
-    return encode_sets(h, reinterpret_cast<const uint8_t*>(d_digests), nullptr, n, true, d_sets, sets_bytes, stream);
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    return encode_sets(cs, h, reinterpret_cast<const uint8_t*>(d_digests), nullptr, n, true, d_sets, sets_bytes, stream);
 }
 
 int bf_insert_region_sets_dev(bf_handle* h, const uint32_t* d_sets, uint64_t stride_bytes, uint32_t nsrc,
                               uint64_t probes_hint, uint32_t* d_any_new, uint32_t* d_status, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
     if (nsrc == 0) return BF_OK;
     if (!d_sets || (reinterpret_cast<uintptr_t>(d_sets) & 15u) || (stride_bytes & 15u))
         return set_err(h, BF_EINVAL, "d_sets and stride_bytes must be 16-byte aligned");
@@ -2247,14 +2039,10 @@ int bf_insert_region_sets_dev(bf_handle* h, const uint32_t* d_sets, uint64_t str
         return set_err(h, BF_EINVAL, "this filter's regions cannot take region sets");
     if (stride_bytes < 4 * bf_sets_header_words(nbins))   // the apply reads both per-region tables
         return set_err(h, BF_EINVAL, "stride_bytes below a set buffer's header and tables");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    BfMarks* mk = prof_begin(h, so.s);
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
+    BfMarks* mk = prof_begin(h, cs.s);
     HIPCHK(h, bf_launch_insert_sets(h->g, h->dev_bytes, rl, nbins, d_sets, stride_bytes / 4, nsrc, probes_hint,
-                                    d_any_new, d_status, so.s, mk));
+                                    d_any_new, d_status, cs.s, mk));
     return BF_OK;
 }
 
@@ -2262,10 +2050,10 @@ int bf_insert_encode_region_sets_dev(bf_handle* h, const uint32_t* d_sets, uint6
                                      uint64_t probes_hint, uint32_t* d_any_new, uint32_t* d_status,
                                      const uint32_t* d_next_digests, uint64_t n_next, uint32_t* d_next_sets,
                                      uint64_t next_sets_bytes, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
     if (nsrc == 0)   // nothing to apply: the encode alone
-        return encode_sets(h, reinterpret_cast<const uint8_t*>(d_next_digests), nullptr, n_next, true, d_next_sets,
+        return encode_sets(cs, h, reinterpret_cast<const uint8_t*>(d_next_digests), nullptr, n_next, true, d_next_sets,
                            next_sets_bytes, stream);
     if (!d_sets || (reinterpret_cast<uintptr_t>(d_sets) & 15u) || (stride_bytes & 15u))
         return set_err(h, BF_EINVAL, "d_sets and stride_bytes must be 16-byte aligned");
@@ -2293,89 +2081,34 @@ int bf_insert_encode_region_sets_dev(bf_handle* h, const uint32_t* d_sets, uint6
     plan.nbins = nbins;
     if (!sets_one_pass(h, n_next, rl, &plan))
         return set_err(h, BF_EINVAL, "a batch of %llu keys does not sort in one pass", (unsigned long long)n_next);
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, pick_stream(h, stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
     if (n_next) {
         int rc = ensure_scratch(h, plan.scratch_bytes);
         if (rc) return rc;
     }
-    BfMarks* mk = prof_begin(h, so.s);
+    BfMarks* mk = prof_begin(h, cs.s);
     if (n_next == 0) {   // an empty next batch: its buffer is the header alone
         HIPCHK(h, bf_launch_encode_sets(h->g, plan, h->dev_bytes, nullptr, nullptr, 0, 0, true, h->d_bin_scratch,
-                                        d_next_sets, std::min<uint64_t>(next_sets_bytes / 4, 0xFFFFFFFFull), so.s,
+                                        d_next_sets, std::min<uint64_t>(next_sets_bytes / 4, 0xFFFFFFFFull), cs.s,
                                         nullptr));
         HIPCHK(h, bf_launch_insert_sets(h->g, h->dev_bytes, rl, nbins, d_sets, stride_bytes / 4, nsrc, probes_hint,
-                                        d_any_new, d_status, so.s, mk));
+                                        d_any_new, d_status, cs.s, mk));
         return BF_OK;
     }
     HIPCHK(h, bf_launch_insert_encode_sets(h->g, plan, h->dev_bytes, rl, nbins, d_sets, stride_bytes / 4, nsrc,
                                            probes_hint, d_any_new, d_status,
                                            reinterpret_cast<const uint8_t*>(d_next_digests), n_next, h->d_bin_scratch,
-                                           d_next_sets, std::min<uint64_t>(next_sets_bytes / 4, 0xFFFFFFFFull), so.s,
+                                           d_next_sets, std::min<uint64_t>(next_sets_bytes / 4, 0xFFFFFFFFull), cs.s,
                                            mk));
     return BF_OK;
 }
 
-int bf_stream(bf_handle* h, void** stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h || !stream) return BF_EINVAL;
-    *stream = reinterpret_cast<void*>(h->stream);
-    return BF_OK;
-}
-
-int bf_device_bits(bf_handle* h, void** d_bits, uint64_t* device_bytes) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
-    if (!h->g.bits) return set_err(h, BF_EINVAL, "an encoder handle (BF_FLAG_ENCODER) holds no bitset");
-    if (d_bits) *d_bits = h->g.bits;
-    if (device_bytes) *device_bytes = h->dev_bytes;
-    return BF_OK;
-}
-
-int bf_profile(bf_handle* h, uint32_t enable) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    int rc = prof_harvest(h);
-    h->profile = enable != 0;
-    return rc;
-}
-
-int bf_profile_read(bf_handle* h, char* names, double* total_ms, uint64_t* launches, uint32_t cap,
-                    uint32_t* n_out, uint32_t reset) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h || !n_out) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    int rc = prof_harvest(h);
-    if (rc) return rc;
-    *n_out = (uint32_t)h->prof_acc.size();
-    for (uint32_t i = 0; i < cap && i < h->prof_acc.size(); ++i) {
-        const bf_handle::ProfAcc& a = h->prof_acc[i];
-        if (names) snprintf(names + (size_t)i * BF_PROFILE_NAME_LEN, BF_PROFILE_NAME_LEN, "%s", a.name.c_str());
-        if (total_ms) total_ms[i] = a.ms;
-        if (launches) launches[i] = a.launches;
-    }
-    if (reset) h->prof_acc.clear();
-    return BF_OK;
-}
-
-int bf_track_dirty(bf_handle* h, uint32_t enable) {
-    if (h && h->multi) return bfm_track_dirty(h->multi, enable);
-    if (!h) return BF_EINVAL;
-    if (h->shards > 1) return set_err(h, BF_EINVAL, "dirty tracking needs a whole-filter handle");
-    return bfi_track_dirty(h, enable);
-}
-
 }  // extern "C"
 
-int bfi_track_dirty(bf_handle* h, uint32_t enable) {
+namespace {
+// Dirty tracking switched on or off (the caller holds the handle's scope).
+int track_dirty(bf_handle* h, uint32_t enable) {
     if (!h->g.bits) return set_err(h, BF_EINVAL, "an encoder handle (BF_FLAG_ENCODER) holds no bitset");
-    std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard dg(h->device);
     HIPCHK(h, hipDeviceSynchronize());   // no launch may still use the map
     if (!enable) {
@@ -2394,17 +2127,17 @@ int bfi_track_dirty(bf_handle* h, uint32_t enable) {
     return BF_OK;
 }
 
-// The changed byte ranges of the handle's own bytes (whole filter: the Redis string; shard:
-// its local bytes), clipped to their trimmed length; clear forgets them.
-int bfi_dirty_local(bf_handle* h, std::vector<uint64_t>* out, bool clear) {
+// The dirty blocks as coalesced (offset, length) byte ranges clipped to the trimmed length *len.
+int dirty_local(CallScope& cs, bf_handle* h, std::vector<uint64_t>* out, uint64_t* len) {
     if (!h->d_dirty) return set_err(h, BF_EINVAL, "dirty tracking is off (bf_track_dirty)");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
+    // The scope's own guard, so that it spans the caller's clearing hipMemset too and the
+    // trimmed-length pass below puts no second guard inside it.  Unchecked here, as it has been:
+    // a failed hipSetDevice is reported by that pass's opening.
+    (void)cs.device();
     HIPCHK(h, hipDeviceSynchronize());   // inserts may have run on any stream
     std::vector<uint8_t> map(h->dirty_blocks);
     HIPCHK(h, hipMemcpy(map.data(), h->d_dirty, h->dirty_blocks, hipMemcpyDeviceToHost));
-    uint64_t len = 0;
-    int rc = device_trimmed_len(h, &len);
+    int rc = device_trimmed_len(cs, h, len);
     if (rc) return rc;
     out->clear();
     for (uint64_t b = 0; b < h->dirty_blocks;) {
@@ -2412,60 +2145,70 @@ int bfi_dirty_local(bf_handle* h, std::vector<uint64_t>* out, bool clear) {
         uint64_t e = b;
         while (e < h->dirty_blocks && map[e]) ++e;
         const uint64_t off = b * BF_DIRTY_BLOCK_BYTES;
-        const uint64_t end = std::min<uint64_t>(e * BF_DIRTY_BLOCK_BYTES, len);
+        const uint64_t end = std::min<uint64_t>(e * BF_DIRTY_BLOCK_BYTES, *len);
         if (end > off) { out->push_back(off); out->push_back(end - off); }
         b = e;
     }
-    if (clear) HIPCHK(h, hipMemset(h->d_dirty, 0, h->dirty_blocks));
     return BF_OK;
 }
-
-int bfi_trimmed_len(bf_handle* h, uint64_t* len) {
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    return device_trimmed_len(h, len);
-}
-
-int bfi_export_local(bf_handle* h, uint64_t offset, uint64_t len, uint8_t* buf) {
-    if (offset > h->dev_bytes || len > h->dev_bytes - offset)
-        return set_err(h, BF_ERANGE, "range [%llu, +%llu) outside the %llu-byte bitset", (unsigned long long)offset,
-                       (unsigned long long)len, (unsigned long long)h->dev_bytes);
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (h->order_valid) HIPCHK(h, hipEventSynchronize(h->order_ev));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (len) HIPCHK(h, hipMemcpy(buf, reinterpret_cast<const uint8_t*>(h->g.bits) + offset, len, hipMemcpyDeviceToHost));
-    return BF_OK;
-}
+}  // namespace
 
 extern "C" {
+
+int bf_stream(bf_handle* h, void** stream) {
+    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
+    if (!h || !stream) return BF_EINVAL;
+    *stream = reinterpret_cast<void*>(h->stream);
+    return BF_OK;
+}
+
+int bf_device_bits(bf_handle* h, void** d_bits, uint64_t* device_bytes) {
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    if (!h->g.bits) return set_err(h, BF_EINVAL, "an encoder handle (BF_FLAG_ENCODER) holds no bitset");
+    if (d_bits) *d_bits = h->g.bits;
+    if (device_bytes) *device_bytes = h->dev_bytes;
+    return BF_OK;
+}
+
+int bf_profile(bf_handle* h, uint32_t enable) {
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
+    DeviceGuard dg(h->device);
+    int rc = prof_harvest(h);
+    h->profile = enable != 0;
+    return rc;
+}
+
+int bf_profile_read(bf_handle* h, char* names, double* total_ms, uint64_t* launches, uint32_t cap,
+                    uint32_t* n_out, uint32_t reset) {
+    if (int rc = single_handle(h)) return rc;
+    if (!n_out) return BF_EINVAL;
+    CallScope cs(h);
+    DeviceGuard dg(h->device);
+    return prof_read(h, names, total_ms, launches, cap, n_out, reset);
+}
+
+int bf_track_dirty(bf_handle* h, uint32_t enable) {
+    if (h && h->multi) return bfm_track_dirty(h->multi, enable);
+    if (!h) return BF_EINVAL;
+    CallScope cs(h);
+    if (h->shards > 1) return set_err(h, BF_EINVAL, "dirty tracking needs a whole-filter handle");
+    return track_dirty(h, enable);
+}
 
 int bf_dirty_ranges(bf_handle* h, uint64_t* ranges, uint32_t cap, uint32_t* n_out, uint64_t* redis_len,
                     uint32_t clear) {
     if (h && h->multi) return n_out ? bfm_dirty_ranges(h->multi, ranges, cap, n_out, redis_len, clear) : BF_EINVAL;
     if (!h || !n_out) return BF_EINVAL;
-    if (!h->d_dirty) return set_err(h, BF_EINVAL, "dirty tracking is off (bf_track_dirty)");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    HIPCHK(h, hipDeviceSynchronize());   // inserts may have run on any stream
-    std::vector<uint8_t> map(h->dirty_blocks);
-    HIPCHK(h, hipMemcpy(map.data(), h->d_dirty, h->dirty_blocks, hipMemcpyDeviceToHost));
-    uint64_t len = 0;
-    int rc = device_trimmed_len(h, &len);
-    if (rc) return rc;
-    if (redis_len) *redis_len = len;
+    CallScope cs(h);
     // adjacent dirty blocks coalesce; everything is clipped to the string's length, so
     // SETRANGE grows the key exactly as the SETBITs would have
     std::vector<uint64_t> out;
-    for (uint64_t b = 0; b < h->dirty_blocks;) {
-        if (!map[b]) { ++b; continue; }
-        uint64_t e = b;
-        while (e < h->dirty_blocks && map[e]) ++e;
-        const uint64_t off = b * BF_DIRTY_BLOCK_BYTES;
-        const uint64_t end = std::min<uint64_t>(e * BF_DIRTY_BLOCK_BYTES, len);
-        if (end > off) { out.push_back(off); out.push_back(end - off); }
-        b = e;
-    }
+    uint64_t len = 0;
+    int rc = dirty_local(cs, h, &out, &len);
+    if (rc) return rc;
+    if (redis_len) *redis_len = len;
     *n_out = (uint32_t)(out.size() / 2);
     if (ranges) {
         if (*n_out > cap) return set_err(h, BF_ERANGE, "%u dirty ranges, room for %u", *n_out, cap);
@@ -2478,18 +2221,57 @@ int bf_dirty_ranges(bf_handle* h, uint64_t* ranges, uint32_t cap, uint32_t* n_ou
 int bf_export_range(bf_handle* h, uint64_t offset, uint64_t len, uint8_t* buf) {
     if (h && h->multi) return (len && !buf) ? BF_EINVAL : bfm_export_range(h->multi, offset, len, buf);
     if (!h || (len && !buf)) return BF_EINVAL;
+    CallScope cs(h);
     if (h->shards > 1) return set_err(h, BF_EINVAL, "partitioned shard: use bf_shard_export");
     if (!h->g.bits) return set_err(h, BF_EINVAL, "an encoder handle (BF_FLAG_ENCODER) holds no bitset");
     if (offset > h->dev_bytes || len > h->dev_bytes - offset)
         return set_err(h, BF_ERANGE, "range [%llu, +%llu) outside the %llu-byte bitset", (unsigned long long)offset,
                        (unsigned long long)len, (unsigned long long)h->dev_bytes);
-    std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard dg(h->device);
     HIPCHK(h, hipDeviceSynchronize());
     if (len) HIPCHK(h, hipMemcpy(buf, reinterpret_cast<const uint8_t*>(h->g.bits) + offset, len,
                                  hipMemcpyDeviceToHost));
     return BF_OK;
 }
+
+}  // extern "C"
+
+// ---- what bf_multi.cpp runs on its per-device handles (bf_multi.h) ----
+
+int bfi_track_dirty(bf_handle* h, uint32_t enable) {
+    CallScope cs(h);
+    return track_dirty(h, enable);
+}
+
+// The changed byte ranges of the handle's own bytes (whole filter: the Redis string; shard:
+// its local bytes), clipped to their trimmed length; clear forgets them.
+int bfi_dirty_local(bf_handle* h, std::vector<uint64_t>* out, bool clear) {
+    CallScope cs(h);
+    uint64_t len = 0;
+    int rc = dirty_local(cs, h, out, &len);
+    if (rc) return rc;
+    if (clear) HIPCHK(h, hipMemset(h->d_dirty, 0, h->dirty_blocks));
+    return BF_OK;
+}
+
+int bfi_trimmed_len(bf_handle* h, uint64_t* len) {
+    CallScope cs(h);
+    return device_trimmed_len(cs, h, len);
+}
+
+int bfi_export_local(bf_handle* h, uint64_t offset, uint64_t len, uint8_t* buf) {
+    CallScope cs(h);
+    if (offset > h->dev_bytes || len > h->dev_bytes - offset)
+        return set_err(h, BF_ERANGE, "range [%llu, +%llu) outside the %llu-byte bitset", (unsigned long long)offset,
+                       (unsigned long long)len, (unsigned long long)h->dev_bytes);
+    DeviceGuard dg(h->device);
+    if (h->order_valid) HIPCHK(h, hipEventSynchronize(h->order_ev));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (len) HIPCHK(h, hipMemcpy(buf, reinterpret_cast<const uint8_t*>(h->g.bits) + offset, len, hipMemcpyDeviceToHost));
+    return BF_OK;
+}
+
+extern "C" {
 
 int bf_insert_plan(const bf_handle* h, uint64_t n, uint32_t* binned, uint64_t* scratch_bytes) {
     if (h && h->multi) return bfm_insert_plan(h->multi, n, binned, scratch_bytes);
@@ -2520,9 +2302,8 @@ int bf_insert_plan_detail(const bf_handle* h, uint64_t n, bf_plan_detail* out) {
     if (!h) return BF_EINVAL;
     const int rc = bf_binned_plan_detail(h->dev_bytes, h->k, n, h->bin_region_log2, 0, out);
     if (rc != BF_OK) return rc;
-    uint32_t b = 0;
-    (void)bf_insert_plan(h, n, &b, nullptr);
-    out->binned = b;
+    BfBinPlan plan{};
+    out->binned = n > 0 && use_binned(h, n, false, &plan) ? 1u : 0u;
     return BF_OK;
 }
 
@@ -2645,25 +2426,18 @@ extern "C" {
 int bf_bitcount(bf_handle* h, uint64_t byte_start, uint64_t byte_len, uint64_t* set_bits) {
     if (h && h->multi) return set_bits ? bfm_bitcount(h->multi, byte_start, byte_len, set_bits) : BF_EINVAL;
     if (!h || !set_bits) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, h->stream);
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
+    CallScope cs(h);
+    if (int krc = handle_open(cs, h, h->stream)) return krc;
     if (int rc = launch_bitcount(h, byte_start, byte_len, h->d_scan + kStatWord, h->stream)) return rc;
     return read_stat_words(h, set_bits, nullptr);
 }
 
 int bf_bitcount_dev(bf_handle* h, uint64_t byte_start, uint64_t byte_len, uint64_t* d_set_bits, void* stream) {
-    if (h && h->multi) return bfm_fail(h->multi, BF_EINVAL, "multi-device handle: use the host-pointer API");
-    if (!h) return BF_EINVAL;
-    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = single_handle(h)) return rc;
+    CallScope cs(h);
     if (!d_set_bits) return set_err(h, BF_EINVAL, "d_set_bits is NULL");
-    DeviceGuard dg(h->device);
-    if (!dg.ok) return set_err(h, BF_EDEVICE, "hipSetDevice(%d) failed", h->device);
-    StreamOrder so(h, reinterpret_cast<hipStream_t>(stream));
-    if (int krc = op_check(h)) return krc;   // a bitset-less handle; an earlier call's bad key offsets
-    return launch_bitcount(h, byte_start, byte_len, reinterpret_cast<unsigned long long*>(d_set_bits), so.s);
+    if (int krc = handle_open(cs, h, pick_stream(h, stream))) return krc;
+    return launch_bitcount(h, byte_start, byte_len, reinterpret_cast<unsigned long long*>(d_set_bits), cs.s);
 }
 
 int bf_bitop(bf_handle* dst, uint32_t op, bf_handle* src, uint8_t* changed, uint64_t* set_bits) {

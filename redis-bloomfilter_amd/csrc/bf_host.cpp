@@ -1,4 +1,4 @@
-// bf_host.cpp — the shared host core of bf_lua and bf_bank (bf_host.h).
+// bf_host.cpp — the shared host core of bf_handle, bf_lua and bf_bank (bf_host.h).
 #include "bf_host.h"
 #include "bfhip.h"
 

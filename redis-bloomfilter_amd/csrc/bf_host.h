@@ -1,8 +1,7 @@
-// bf_host.h — the host plumbing around every launch, shared by bf_lua (bf_lua.hip) and bf_bank
-// (bf_bank.hip), and in part by bf_multi.cpp: the common state, the error formatter and check
-// macro, the device and stream-order guards, the call scope that holds them with the mutex, the
-// key-status report and the per-kernel profile.  Host only.  (bf_handle in bf_api.cpp still has
-// its own copies of these pieces.)
+// bf_host.h — the host plumbing around every launch, shared by bf_handle (bf_api.cpp), bf_lua
+// (bf_lua.hip) and bf_bank (bf_bank.hip), and in part by bf_multi.cpp: the common state, the error
+// formatter and check macro, the device and stream-order guards, the call scope that holds them
+// with the mutex, the key-status report and the per-kernel profile.  Host only.
 #pragma once
 #include "bf_internal.h"
 
@@ -13,7 +12,7 @@
 
 struct BfProfAcc { std::string name; double ms; uint64_t launches; };
 
-// What bf_lua and bf_bank derive from.  The handle types are opaque in bfhip.h.
+// What bf_handle, bf_lua and bf_bank derive from.  The handle types are opaque in bfhip.h.
 struct BfHostCore {
     std::mutex mu;
     int device = 0;
