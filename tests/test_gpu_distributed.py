@@ -178,6 +178,53 @@ def test_route_windows(pkg, oracle, m, k, P, b):
     e.close()
 
 
+def check_chunk_route(oracle, D, m, k, P, b, nh, cap, tiles, dbytes, S, send, slot, counts, dirb, buf, offs):
+    """One rank's bf_route_chunks_dev output against the oracle: every window holds exactly its owner's
+    (key, local offset) pairs, and its directory partitions it into one run per route tile (S: the
+    superbins per window of bf_route_chunk_info)."""
+    nwin = P * nh
+    tile_keys = 2048 if k <= 6 else 1024
+    rank_off = 4 * tiles + 2 * (S + 1) * tiles          # start[tiles], tab[(S + 1) * tiles], then rank[tiles]
+    claim_off = -(-(rank_off + 2 * tiles) // 8) * 8    # ... and the 8-byte claim counter
+    idx = oracle.indexes_many(buf, offs, m, k).reshape(-1)
+    owner, local = D.block_owner_local(idx, P, b)
+    win = owner.astype(np.int64) * nh + (local >> np.uint64(32)).astype(np.int64)
+    want_c = np.bincount(win, minlength=nwin)
+    c = counts.cpu().numpy()
+    assert c.tolist() == want_c.tolist()
+    s_np = send.cpu().numpy().view(np.uint32).astype(np.uint64)
+    sl = slot.cpu().numpy().view(np.uint16).astype(np.int64)
+    d = dirb.cpu().numpy()
+    key_of = np.arange(len(idx)) // k
+    for w in range(nwin):
+        dw = d[w * dbytes:(w + 1) * dbytes]
+        start = dw[: 4 * tiles].view(np.uint32).astype(np.int64)
+        tab = dw[4 * tiles: 4 * tiles + 2 * (S + 1) * tiles].view(np.uint16).reshape(S + 1, tiles)
+        length = tab[S].astype(np.int64)
+        assert (np.diff(tab.astype(np.int64), axis=0) >= 0).all()   # superbin runs in order
+        # the chunks tile [0, count) of the window, one per route tile, runs monotone inside
+        live = length > 0
+        spans = sorted(zip(start[live].tolist(), (start[live] + length[live]).tolist()))
+        at = 0
+        for a, e in spans:
+            assert a == at
+            at = e
+        assert at == int(want_c[w])
+        # the rank table lists the claimed runs in window order (the owner's ranked chunks)
+        rank = dw[rank_off: rank_off + 2 * tiles].view(np.uint16).astype(np.int64)
+        nclaim = int(dw[claim_off: claim_off + 8].view(np.uint64)[0]) >> 40
+        assert nclaim == int(live.sum()) and (rank[nclaim:] == 0).all()
+        ranked = rank[:nclaim] - 1
+        assert sorted(ranked.tolist()) == np.flatnonzero(live).tolist()
+        assert (np.diff(start[ranked]) > 0).all()
+        got, keys_w = [], []
+        for t in np.flatnonzero(live):
+            seg = slice(w * cap + int(start[t]), w * cap + int(start[t] + length[t]))
+            got += (s_np[seg] | np.uint64((w % nh) << 32)).tolist()
+            keys_w += (sl[seg] + t * tile_keys).tolist()
+        assert sorted(zip(keys_w, got)) == sorted(zip(key_of[win == w].tolist(), local[win == w].tolist()))
+
+
 # every owner form on the small and north-star filters; the 10B x 4 and 200B x 8 filters (the
 # slow cases) on one form each: the L2 sweep, and the sorted test their owners take
 @pytest.mark.parametrize("m,k,P,b,owner", [
@@ -236,43 +283,7 @@ def test_chunked_windows(pkg, oracle, monkeypatch, m, k, P, b, owner):
         return out
 
     def check_route(send, slot, counts, dirb, buf, offs):
-        idx = oracle.indexes_many(buf, offs, m, k).reshape(-1)
-        owner, local = D.block_owner_local(idx, P, b)
-        win = owner.astype(np.int64) * nh + (local >> np.uint64(32)).astype(np.int64)
-        want_c = np.bincount(win, minlength=nwin)
-        c = counts.cpu().numpy()
-        assert c.tolist() == want_c.tolist()
-        s_np = send.cpu().numpy().view(np.uint32).astype(np.uint64)
-        sl = slot.cpu().numpy().view(np.uint16).astype(np.int64)
-        d = dirb.cpu().numpy()
-        key_of = np.arange(len(idx)) // k
-        for w in range(nwin):
-            dw = d[w * dbytes:(w + 1) * dbytes]
-            start = dw[: 4 * tiles].view(np.uint32).astype(np.int64)
-            tab = dw[4 * tiles: 4 * tiles + 2 * (S + 1) * tiles].view(np.uint16).reshape(S + 1, tiles)
-            length = tab[S].astype(np.int64)
-            assert (np.diff(tab.astype(np.int64), axis=0) >= 0).all()   # superbin runs in order
-            # the chunks tile [0, count) of the window, one per route tile, runs monotone inside
-            live = length > 0
-            spans = sorted(zip(start[live].tolist(), (start[live] + length[live]).tolist()))
-            at = 0
-            for a, e in spans:
-                assert a == at
-                at = e
-            assert at == int(want_c[w])
-            # the rank table lists the claimed runs in window order (the owner's ranked chunks)
-            rank = dw[rank_off: rank_off + 2 * tiles].view(np.uint16).astype(np.int64)
-            nclaim = int(dw[claim_off: claim_off + 8].view(np.uint64)[0]) >> 40
-            assert nclaim == int(live.sum()) and (rank[nclaim:] == 0).all()
-            ranked = rank[:nclaim] - 1
-            assert sorted(ranked.tolist()) == np.flatnonzero(live).tolist()
-            assert (np.diff(start[ranked]) > 0).all()
-            got, keys_w = [], []
-            for t in np.flatnonzero(live):
-                seg = slice(w * cap + int(start[t]), w * cap + int(start[t] + length[t]))
-                got += (s_np[seg] | np.uint64((w % nh) << 32)).tolist()
-                keys_w += (sl[seg] + t * tile_keys).tolist()
-            assert sorted(zip(keys_w, got)) == sorted(zip(key_of[win == w].tolist(), local[win == w].tolist()))
+        check_chunk_route(oracle, D, m, k, P, b, nh, cap, tiles, dbytes, S, send, slot, counts, dirb, buf, offs)
 
     def deliver(routed, o):
         recv = torch.cat([routed[src][0][(o * nh + h) * cap:(o * nh + h + 1) * cap] for h in range(nh)
