@@ -301,6 +301,22 @@ int  bf_binned_plan_detail(uint64_t device_bytes, uint32_t k, uint64_t n, uint32
  * multi-device handle answers for its first device. */
 int  bf_insert_plan_detail(const bf_handle* h, uint64_t n, bf_plan_detail* out);
 
+/* Which form the sequential insert (per_key_new of bf_insert_many*, every bf_lua_insert_many*)
+ * takes for ONE chunk of n keys on a filter or layer of m bits and k hashes: no launch,
+ * read-only, handle-free and host-only, from the predicates the launch code itself branches
+ * on.  Each output is nullable.  *slots is the first-index table's entries: the hash table's
+ * slots (a power of two of at least 1024 and at least 2 n k), one per filter bit (m) for the
+ * direct form, the regions of 2^14 bits for the binned form.  *scratch_bytes is what a chunk
+ * needs.  A call cuts its batch into chunks of at most bf_seq_plan_chunk's *chunk_keys keys
+ * (the Lua layout also cuts where a layer fills); each chunk picks its own form.  k == 0,
+ * k > BF_MAX_K and m == 0 are BF_EINVAL. */
+#define BF_SEQ_HASH   0u
+#define BF_SEQ_DIRECT 1u
+#define BF_SEQ_BINNED 2u
+int  bf_seq_plan(uint64_t n, uint32_t k, uint64_t m, uint32_t* form /* BF_SEQ_* */, uint64_t* slots,
+                 uint64_t* scratch_bytes);
+int  bf_seq_plan_chunk(uint32_t k, uint64_t* chunk_keys);
+
 /* ---- incremental Redis sync.  With tracking on, every insert
  *      (direct, binned and sequential paths) marks the BF_DIRTY_BLOCK_BYTES blocks
  *      of the Redis string it may have changed; imports mark everything; bf_clear

@@ -111,6 +111,8 @@ SIGNATURES = {
     "bf_insert_plan": (ctypes.c_int, [_vp, _u64, _u32p, _u64p]),
     "bf_binned_plan_detail": (ctypes.c_int, [_u64, _u32, _u64, _u32, _u32, ctypes.POINTER(bf_plan_detail)]),
     "bf_insert_plan_detail": (ctypes.c_int, [_vp, _u64, ctypes.POINTER(bf_plan_detail)]),
+    "bf_seq_plan": (ctypes.c_int, [_u64, _u32, _u64, _u32p, _u64p, _u64p]),
+    "bf_seq_plan_chunk": (ctypes.c_int, [_u32, _u64p]),
     "bf_track_dirty": (ctypes.c_int, [_vp, _u32]),
     "bf_dirty_ranges": (ctypes.c_int, [_vp, _u64p, _u32, _u32p, _u64p, _u32]),
     "bf_export_range": (ctypes.c_int, [_vp, _u64, _u64, _vp]),
@@ -328,6 +330,24 @@ def binned_plan_detail(device_bytes: int, k: int, n: int, region_log2_pref: int 
     _check(load().bf_binned_plan_detail(int(device_bytes), int(k), int(n), int(region_log2_pref),
                                         int(compute_units), ctypes.byref(d)))
     return d.as_dict()
+
+
+SEQ_FORMS = ("hash", "direct", "binned")   # BF_SEQ_HASH, BF_SEQ_DIRECT, BF_SEQ_BINNED
+
+
+def seq_plan(n: int, k: int, m: int) -> dict:
+    """How the sequential insert runs one chunk of n keys on a filter or layer of m bits and k
+    hashes (bf_seq_plan, bf_seq_plan_chunk): host-only, no handle, no GPU needed.  "form" is
+    0 hash / 1 direct / 2 binned (SEQ_FORMS), "slots" the first-index table's entries,
+    "scratch_bytes" the chunk's scratch, "chunk_keys" the most keys a chunk of this k holds."""
+    form, slots, scratch, chunk = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    for rc in (load().bf_seq_plan(int(n), int(k), int(m), ctypes.byref(form), ctypes.byref(slots),
+                                  ctypes.byref(scratch)),
+               load().bf_seq_plan_chunk(int(k), ctypes.byref(chunk))):
+        if rc:
+            raise ArgumentError("bf_seq_plan(%r, %r, %r) failed" % (n, k, m))
+    return {"form": int(form.value), "slots": int(slots.value), "scratch_bytes": int(scratch.value),
+            "chunk_keys": int(chunk.value)}
 
 
 def check_offsets(offsets: np.ndarray) -> None:

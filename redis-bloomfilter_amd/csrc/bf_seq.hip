@@ -24,6 +24,7 @@
 // against — is !new(j).  The probe indices are i0 .. i0+k-1: 0-based for the
 // ruby driver (ruby.rb:50), 1-based for the Lua scripts (add.lua:37).
 #include "bf_device.h"
+#include "bfhip.h"   // bf_seq_plan
 
 using namespace bfdev;
 
@@ -396,6 +397,23 @@ uint64_t bf_seq_scratch_bytes(uint64_t n, uint32_t k, uint64_t m) {
     if (seq_binned(n, m)) return seq_bin_scratch_bytes(n, k, m);
     const uint64_t tab = seq_direct(n, k, m) ? align256(m * 4) : align256(seq_slots(n, k) * 8) + align256(seq_slots(n, k) * 4);
     return tab + align256(n * 16) + align256(n * 8);
+}
+
+// Which form the two launchers below take for a chunk of n keys: the predicates they branch on.
+extern "C" int bf_seq_plan(uint64_t n, uint32_t k, uint64_t m, uint32_t* form, uint64_t* slots,
+                           uint64_t* scratch_bytes) {
+    if (k == 0 || k > BF_MAX_K || m == 0) return BF_EINVAL;
+    const bool binned = seq_binned(n, m), direct = !binned && seq_direct(n, k, m);
+    if (form) *form = binned ? BF_SEQ_BINNED : direct ? BF_SEQ_DIRECT : BF_SEQ_HASH;
+    if (slots) *slots = binned ? seq_regions(m) : direct ? m : seq_slots(n, k);
+    if (scratch_bytes) *scratch_bytes = bf_seq_scratch_bytes(n, k, m);
+    return BF_OK;
+}
+
+extern "C" int bf_seq_plan_chunk(uint32_t k, uint64_t* chunk_keys) {
+    if (k == 0 || k > BF_MAX_K || !chunk_keys) return BF_EINVAL;
+    *chunk_keys = bf_seq_chunk_keys(k);
+    return BF_OK;
 }
 
 hipError_t bf_launch_seq_candidates(const BfGeom& g, uint32_t i0, const uint8_t* keys16, const uint64_t* offsets,

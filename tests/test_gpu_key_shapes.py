@@ -390,7 +390,8 @@ def test_site_f2_l2_test_side_batch(pkg, monkeypatch, shape):
 
 # (form, m, k, least keys): bf_seq.hip takes the binned form from 4096 keys on filters of up to
 # 2^27 bits; below that the one-word-per-bit table where 4 m <= 12 * slots(n, k) (9585 bits), and
-# the hash table elsewhere (9,585,058 bits).
+# the hash table elsewhere (9,585,058 bits).  tests/test_seq_plan_abi.py asserts these forms with
+# bf_seq_plan at the batch sizes used here (test_key_shape_site_g_forms).
 SEQ_FORMS = [("direct", 9585, 6, 0), ("binned", 9585, 6, 4096), ("binned", 95851, 7, 4096), ("hash", 9585058, 7, 0)]
 
 
