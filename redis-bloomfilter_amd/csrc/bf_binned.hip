@@ -99,6 +99,27 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w, u
     return r;
 }
 
+// Hashes a front tile's keys: H0 gets the SHA-1 words of lane t's key, H1 those of key kTile + t
+// of a two-keys-per-lane tile (tk > kTile, workgroup-uniform).  The keys are staged in the
+// caller's LDS (s_off, s_stage), kTile at a time.  Shared by bin_front_body and route_front_body
+// (their digest forms read H0 / H1 from the digest array instead: folding those three lines in
+// here too moved the digest kernels' registers and spills).  Contains barriers: every lane must
+// call it.
+__device__ __forceinline__ void tile_sha1_words(const uint8_t* keys16, const uint64_t* offsets, uint64_t bias,
+                                                uint64_t key0, uint32_t tk, uint32_t* key_status, uint64_t* s_off,
+                                                uint4* s_stage, uint4& H0, uint4& H1) {
+    auto hash = [&](uint64_t first, uint32_t cnt, uint4& Hd) {
+        for_key_tile<kTile, kStageVec>(keys16, offsets, bias, first, cnt, s_off, s_stage, key_status,
+            [&](auto staged, uint32_t, const uint32_t* src, uint32_t s, uint32_t L) {
+                uint32_t H[5];
+                sha1_any<decltype(staged)::value>(src, s, L, H);
+                Hd = make_uint4(H[0], H[1], H[2], H[3]);
+            });
+    };
+    hash(key0, tk < (uint32_t)kTile ? tk : kTile, H0);
+    if (tk > (uint32_t)kTile) hash(key0 + kTile, tk - kTile, H1);   // each lane's second key
+}
+
 // DIG: the keys arrive as their SHA-1 words (keys16 is then a uint4 array, 16 B per key,
 // offsets unused): no staging, no hashing — the front pass is a partition pass.
 template <bool KEYS, int SLOTS, bool DIG = false>
@@ -137,20 +158,7 @@ __device__ __forceinline__ void bin_front_body(BfGeom g, const uint8_t* __restri
             if (t < tk) H0 = dig[key0 + t];
             if (kTile + t < tk) H1 = dig[key0 + kTile + t];
         } else {
-            for_key_tile<kTile, kStageVec>(keys16, offsets, bias, key0, tk < (uint32_t)kTile ? tk : kTile, s_off,
-                                           s_stage, g.key_status, [&](auto staged, uint32_t, const uint32_t* src, uint32_t s, uint32_t L) {
-                uint32_t H[5];
-                sha1_any<decltype(staged)::value>(src, s, L, H);
-                H0 = make_uint4(H[0], H[1], H[2], H[3]);
-            });
-            if (tk > (uint32_t)kTile) {   // workgroup-uniform: the second key of each lane
-                for_key_tile<kTile, kStageVec>(keys16, offsets, bias, key0 + kTile, tk - kTile, s_off, s_stage,
-                    g.key_status, [&](auto staged, uint32_t, const uint32_t* src, uint32_t s, uint32_t L) {
-                        uint32_t H[5];
-                        sha1_any<decltype(staged)::value>(src, s, L, H);
-                        H1 = make_uint4(H[0], H[1], H[2], H[3]);
-                    });
-            }
+            tile_sha1_words(keys16, offsets, bias, key0, tk, g.key_status, s_off, s_stage, H0, H1);
         }
         const bool live0 = t < tk;
         const bool live1 = kpl == 2 && kTile + t < tk;
@@ -644,24 +652,11 @@ __device__ __forceinline__ void route_front_body(BfGeom g, const uint8_t* __rest
         const uint32_t tk = (uint32_t)((n - key0) < (uint64_t)tile_keys ? (n - key0) : tile_keys);
         uint4 H0 = make_uint4(0, 0, 0, 0), H1 = make_uint4(0, 0, 0, 0);
         if constexpr (DIG) {   // the keys' SHA-1 words, hashed earlier (bf_route_chunks_digests_dev)
-            const uint4* dg = reinterpret_cast<const uint4*>(keys16);
-            if (t < tk) H0 = dg[key0 + t];
-            if (kTile + t < tk) H1 = dg[key0 + kTile + t];
+            const uint4* dig = reinterpret_cast<const uint4*>(keys16);
+            if (t < tk) H0 = dig[key0 + t];
+            if (kTile + t < tk) H1 = dig[key0 + kTile + t];
         } else {
-        for_key_tile<kTile, kStageVec>(keys16, offsets, bias, key0, tk < (uint32_t)kTile ? tk : kTile, s_off, s_stage,
-            g.key_status, [&](auto staged, uint32_t, const uint32_t* src, uint32_t s, uint32_t L) {
-                uint32_t H[5];
-                sha1_any<decltype(staged)::value>(src, s, L, H);
-                H0 = make_uint4(H[0], H[1], H[2], H[3]);
-            });
-        if (tk > (uint32_t)kTile) {
-            for_key_tile<kTile, kStageVec>(keys16, offsets, bias, key0 + kTile, tk - kTile, s_off, s_stage,
-                g.key_status, [&](auto staged, uint32_t, const uint32_t* src, uint32_t s, uint32_t L) {
-                    uint32_t H[5];
-                    sha1_any<decltype(staged)::value>(src, s, L, H);
-                    H1 = make_uint4(H[0], H[1], H[2], H[3]);
-                });
-        }
+            tile_sha1_words(keys16, offsets, bias, key0, tk, g.key_status, s_off, s_stage, H0, H1);
         }
         const bool live0 = t < tk;
         const bool live1 = kpl == 2 && kTile + t < tk;
@@ -1060,6 +1055,99 @@ uint32_t mid_grid(uint32_t nsup, uint32_t nq) {
     return mid_grouped(nsup) ? 8u * ((nsup + 7u) / 8u) * nq * kMidParts : nsup * nq * kMidParts;
 }
 
+// What the two bin_mid kernels share.  A workgroup's share of window w = (superbin sb, group q):
+// chunk blocks [c_lo, c_hi) of the window's nblk, part p of kMidParts taking an equal share.
+// Filled in two steps around the kernels' early exit: share(), then, only if the part has a
+// block, buckets(); mid_sort_blocks needs both.  (One init that returns false for an empty share
+// reads better and was tried first: it cost the four bin_mid_chunks_kernel forms 4 SGPRs each.)
+struct MidWindow {
+    uint32_t wbase, E;       // the window's place and length in level 2
+    uint32_t c_lo, c_hi;     // this part's blocks: none if c_lo >= c_hi (workgroup-uniform)
+    uint32_t b0;             // the window's first chunk block (tabs column)
+    uint32_t R, rmask;       // regions per superbin, region-local offset mask
+    uint32_t sub, NB, smask_b;
+    __device__ __forceinline__ void share(const uint32_t* base, uint32_t w, uint32_t part) {
+        wbase = base[w];
+        E = base[w + 1] - wbase;
+        const uint32_t nblk = (E + kBlockProbes - 1) / kBlockProbes;
+        c_lo = (uint32_t)((uint64_t)nblk * part / kMidParts);
+        c_hi = (uint32_t)((uint64_t)nblk * (part + 1) / kMidParts);
+    }
+    __device__ __forceinline__ void buckets(const uint32_t* cb_base, uint32_t w, uint32_t region_log2,
+                                            uint32_t rel_log2) {
+        b0 = cb_base[w];
+        R = 1u << rel_log2;
+        rmask = (1u << region_log2) - 1u;
+        // Sort buckets = (region, low offset bits): at least kMidBuckets LDS counters however few
+        // the regions per superbin, so that the rank atomics do not pile onto R words (a 150 MB
+        // shard has R = 16); a region's sub-buckets are consecutive, so its probes stay one run.
+        sub = 0;
+        while ((R << sub) < kMidBuckets) ++sub;
+        NB = R << sub;
+        smask_b = (1u << sub) - 1u;
+    }
+};
+
+// The block loop: load(f0, lv, kv) gathers the window's entries [f0, f0 + kBlockProbes) (lv:
+// superbin-local offsets, 0xFFFFFFFF for none; kv: their keys); each block is counting-sorted
+// by region in LDS and written contiguously with its table of region boundaries, while the
+// next block's loads are in flight.  Contains barriers: every lane must call it.
+template <bool KEYS, typename Load>
+__device__ __forceinline__ void mid_sort_blocks(const MidWindow& m, uint32_t region_log2, uint64_t max_chunks,
+                                                uint16_t* tabs, uint32_t* level2, uint32_t* level2_key,
+                                                uint32_t* s_cnt, uint32_t* s_w, uint32_t* s_sorted, uint32_t* s_key,
+                                                Load&& load) {
+    const uint32_t t = threadIdx.x;
+    const uint32_t E = m.E, c_hi = m.c_hi, sub = m.sub, NB = m.NB, smask_b = m.smask_b;
+    uint32_t lv[kChunkPerLane], kv[kChunkPerLane];
+    load(m.c_lo * kBlockProbes, lv, kv);
+    for (uint32_t c = m.c_lo; c < c_hi; ++c) {
+        const uint32_t f0 = c * kBlockProbes;
+        const uint32_t f1 = (E - f0 < kBlockProbes) ? E : f0 + kBlockProbes;
+        if (t < NB) s_cnt[t] = 0;
+        __syncthreads();   // also orders the previous block's reads of s_sorted / s_cnt
+        uint32_t tag[kChunkPerLane];
+#pragma unroll
+        for (int u = 0; u < kChunkPerLane; ++u) {
+            tag[u] = 0xFFFFFFFFu;
+            if (lv[u] != 0xFFFFFFFFu) {
+                const uint32_t bk = ((lv[u] >> region_log2) << sub) | (lv[u] & smask_b);
+                tag[u] = (bk << 16) | atomicAdd(s_cnt + bk, 1u);
+            }
+        }
+        uint32_t nlv[kChunkPerLane], nkv[kChunkPerLane];
+        if (c + 1 < c_hi) load(f0 + kBlockProbes, nlv, nkv);   // next block in flight
+        __syncthreads();
+        const uint32_t cn = t < NB ? s_cnt[t] : 0u;
+        const uint32_t cex = block_excl_scan(cn, s_w, nullptr);   // its barriers order the s_cnt reads first
+        if (!(t & smask_b) && (t >> sub) <= m.R)
+            tabs[(uint64_t)(t >> sub) * max_chunks + m.b0 + c] = (uint16_t)cex;   // [region][block]
+        if (t < NB) s_cnt[t] = cex;
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kChunkPerLane; ++u) {
+            if (tag[u] != 0xFFFFFFFFu) {
+                const uint32_t d = s_cnt[tag[u] >> 16] + (tag[u] & 0xFFFFu);
+                s_sorted[d] = lv[u] & m.rmask;
+                if constexpr (KEYS) s_key[d] = kv[u];
+            }
+        }
+        __syncthreads();
+        const uint32_t out0 = m.wbase + f0;
+        for (uint32_t j = t; j < f1 - f0; j += kTile) {
+            stage_store(level2 + out0 + j, s_sorted[j]);
+            if constexpr (KEYS) level2_key[out0 + j] = s_key[j];
+        }
+        if (c + 1 < c_hi) {
+#pragma unroll
+            for (int u = 0; u < kChunkPerLane; ++u) {
+                lv[u] = nlv[u];
+                kv[u] = nkv[u];
+            }
+        }
+    }
+}
+
 // One workgroup per (window, part): window w = (superbin sb, group q)
 // concatenates superbin sb's runs from the group's tiles in tile order; it is
 // cut into chunk blocks of kBlockProbes, and part p of kMidParts takes an equal
@@ -1081,26 +1169,15 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     __shared__ uint32_t s_sorted[kBlockProbes];
     __shared__ uint32_t s_key[KEYS ? kBlockProbes : 1];
     const uint32_t t = threadIdx.x;
-    uint32_t w_q, w_part;
-    const uint32_t sb = mid_superbin(nsup, nq, mid_grouped(nsup), &w_q, &w_part);   // XCD-grouped
+    uint32_t q, part;
+    const uint32_t sb = mid_superbin(nsup, nq, mid_grouped(nsup), &q, &part);   // XCD-grouped
     if (sb >= nsup) return;   // workgroup-uniform: the grid is rounded up to whole XCD rows
-    const uint32_t q = w_q, part = w_part;
     const uint32_t w = sb * nq + q;
-    const uint32_t wbase = base[w];
-    const uint32_t E = base[w + 1] - wbase;
-    const uint32_t nblk = (E + kBlockProbes - 1) / kBlockProbes;
-    const uint32_t c_lo = (uint32_t)((uint64_t)nblk * part / kMidParts);
-    const uint32_t c_hi = (uint32_t)((uint64_t)nblk * (part + 1) / kMidParts);
-    if (c_lo >= c_hi) return;   // workgroup-uniform
-    const uint32_t b0 = cb_base[w];
-    const uint32_t R = 1u << rel_log2;
-    const uint32_t rmask = (1u << region_log2) - 1u;
-    // Sort buckets = (region, low offset bits): at least kMidBuckets LDS counters however few
-    // the regions per superbin, so that the rank atomics do not pile onto R words (a 150 MB
-    // shard has R = 16); a region's sub-buckets are consecutive, so its probes stay one run.
-    uint32_t sub = 0;
-    while ((R << sub) < kMidBuckets) ++sub;
-    const uint32_t NB = R << sub, smask_b = (1u << sub) - 1u;
+    MidWindow m;
+    m.share(base, w, part);
+    if (m.c_lo >= m.c_hi) return;   // workgroup-uniform
+    m.buckets(cb_base, w, region_log2, rel_log2);
+    const uint32_t E = m.E;   // for the load callable below
     // run table of the group's tiles (consecutive lanes, consecutive tiles: coalesced)
     const uint64_t tlo = (uint64_t)q * tiles_per_group;
     const uint64_t thi = (tlo + tiles_per_group < ntiles) ? tlo + tiles_per_group : ntiles;
@@ -1136,53 +1213,7 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(8, 8))) v
             }
         }
     };
-    uint32_t lv[kChunkPerLane], kv[kChunkPerLane];
-    load(c_lo * kBlockProbes, lv, kv);
-    for (uint32_t c = c_lo; c < c_hi; ++c) {
-        const uint32_t f0 = c * kBlockProbes;
-        const uint32_t f1 = (E - f0 < kBlockProbes) ? E : f0 + kBlockProbes;
-        if (t < NB) s_cnt[t] = 0;
-        __syncthreads();   // also orders the previous block's reads of s_sorted / s_cnt
-        uint32_t tag[kChunkPerLane];
-#pragma unroll
-        for (int u = 0; u < kChunkPerLane; ++u) {
-            tag[u] = 0xFFFFFFFFu;
-            if (lv[u] != 0xFFFFFFFFu) {
-                const uint32_t bk = ((lv[u] >> region_log2) << sub) | (lv[u] & smask_b);
-                tag[u] = (bk << 16) | atomicAdd(s_cnt + bk, 1u);
-            }
-        }
-        uint32_t nlv[kChunkPerLane], nkv[kChunkPerLane];
-        if (c + 1 < c_hi) load(f0 + kBlockProbes, nlv, nkv);   // next block in flight
-        __syncthreads();
-        const uint32_t cn = t < NB ? s_cnt[t] : 0u;
-        const uint32_t cex = block_excl_scan(cn, s_w, nullptr);   // its barriers order the s_cnt reads first
-        if (!(t & smask_b) && (t >> sub) <= R)
-            tabs[(uint64_t)(t >> sub) * max_chunks + b0 + c] = (uint16_t)cex;   // [region][block]
-        if (t < NB) s_cnt[t] = cex;
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kChunkPerLane; ++u) {
-            if (tag[u] != 0xFFFFFFFFu) {
-                const uint32_t d = s_cnt[tag[u] >> 16] + (tag[u] & 0xFFFFu);
-                s_sorted[d] = lv[u] & rmask;
-                if constexpr (KEYS) s_key[d] = kv[u];
-            }
-        }
-        __syncthreads();
-        const uint32_t out0 = wbase + f0;
-        for (uint32_t j = t; j < f1 - f0; j += kTile) {
-            stage_store(level2 + out0 + j, s_sorted[j]);
-            if constexpr (KEYS) level2_key[out0 + j] = s_key[j];
-        }
-        if (c + 1 < c_hi) {
-#pragma unroll
-            for (int u = 0; u < kChunkPerLane; ++u) {
-                lv[u] = nlv[u];
-                kv[u] = nkv[u];
-            }
-        }
-    }
+    mid_sort_blocks<KEYS>(m, region_log2, max_chunks, tabs, level2, level2_key, s_cnt, s_w, s_sorted, s_key, load);
 }
 
 // Region r's probes: one run in each chunk block of its superbin.  Calls
@@ -1921,24 +1952,16 @@ void bin_mid_chunks_kernel(BfChunkIn ci, uint32_t nsup, uint32_t nq, uint32_t re
     __shared__ uint32_t s_sorted[kBlockProbes];
     __shared__ uint32_t s_key[KEYS ? kBlockProbes : 1];
     const uint32_t t = threadIdx.x;
-    uint32_t w_q, w_part;
+    uint32_t q, part;
     // linear order: the owner's few superbins (36 at P = 8) would leave XCDs unevenly loaded
     // grouped (0.405 vs 0.381 ms)
-    const uint32_t sb = mid_superbin(nsup, nq, false, &w_q, &w_part);
-    const uint32_t q = w_q, part = w_part;
+    const uint32_t sb = mid_superbin(nsup, nq, false, &q, &part);
     const uint32_t w = sb * nq + q;
-    const uint32_t wbase = base[w];
-    const uint32_t E = base[w + 1] - wbase;
-    const uint32_t nblk = (E + kBlockProbes - 1) / kBlockProbes;
-    const uint32_t c_lo = (uint32_t)((uint64_t)nblk * part / kMidParts);
-    const uint32_t c_hi = (uint32_t)((uint64_t)nblk * (part + 1) / kMidParts);
-    if (c_lo >= c_hi) return;   // workgroup-uniform
-    const uint32_t b0 = cb_base[w];
-    const uint32_t R = 1u << rel_log2;
-    const uint32_t rmask = (1u << region_log2) - 1u;
-    uint32_t sub = 0;
-    while ((R << sub) < kMidBuckets) ++sub;
-    const uint32_t NB = R << sub, smask_b = (1u << sub) - 1u;
+    MidWindow m;
+    m.share(base, w, part);
+    if (m.c_lo >= m.c_hi) return;   // workgroup-uniform
+    m.buckets(cb_base, w, region_log2, rel_log2);
+    const uint32_t E = m.E;   // for the load callable below
     const uint32_t h = sb / ci.S, lsb = sb - h * ci.S;
     const uint64_t hoff = (uint64_t)h << 32;
     const uint32_t smask = (1u << ci.sup_log2) - 1u;
@@ -1983,53 +2006,7 @@ void bin_mid_chunks_kernel(BfChunkIn ci, uint32_t nsup, uint32_t nq, uint32_t re
             }
         }
     };
-    uint32_t lv[kChunkPerLane], kv[kChunkPerLane];
-    load(c_lo * kBlockProbes, lv, kv);
-    for (uint32_t c = c_lo; c < c_hi; ++c) {
-        const uint32_t f0 = c * kBlockProbes;
-        const uint32_t f1 = (E - f0 < kBlockProbes) ? E : f0 + kBlockProbes;
-        if (t < NB) s_cnt[t] = 0;
-        __syncthreads();
-        uint32_t tag[kChunkPerLane];
-#pragma unroll
-        for (int u = 0; u < kChunkPerLane; ++u) {
-            tag[u] = 0xFFFFFFFFu;
-            if (lv[u] != 0xFFFFFFFFu) {
-                const uint32_t bk = ((lv[u] >> region_log2) << sub) | (lv[u] & smask_b);
-                tag[u] = (bk << 16) | atomicAdd(s_cnt + bk, 1u);
-            }
-        }
-        uint32_t nlv[kChunkPerLane], nkv[kChunkPerLane];
-        if (c + 1 < c_hi) load(f0 + kBlockProbes, nlv, nkv);   // next block in flight
-        __syncthreads();
-        const uint32_t cn = t < NB ? s_cnt[t] : 0u;
-        const uint32_t cex = block_excl_scan(cn, s_w, nullptr);
-        if (!(t & smask_b) && (t >> sub) <= R)
-            tabs[(uint64_t)(t >> sub) * max_chunks + b0 + c] = (uint16_t)cex;   // [region][block]
-        if (t < NB) s_cnt[t] = cex;
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kChunkPerLane; ++u) {
-            if (tag[u] != 0xFFFFFFFFu) {
-                const uint32_t d = s_cnt[tag[u] >> 16] + (tag[u] & 0xFFFFu);
-                s_sorted[d] = lv[u] & rmask;
-                if constexpr (KEYS) s_key[d] = kv[u];
-            }
-        }
-        __syncthreads();
-        const uint32_t out0 = wbase + f0;
-        for (uint32_t j = t; j < f1 - f0; j += kTile) {
-            stage_store(level2 + out0 + j, s_sorted[j]);
-            if constexpr (KEYS) level2_key[out0 + j] = s_key[j];
-        }
-        if (c + 1 < c_hi) {
-#pragma unroll
-            for (int u = 0; u < kChunkPerLane; ++u) {
-                lv[u] = nlv[u];
-                kv[u] = nkv[u];
-            }
-        }
-    }
+    mid_sort_blocks<KEYS>(m, region_log2, max_chunks, tabs, level2, level2_key, s_cnt, s_w, s_sorted, s_key, load);
 }
 
 // Requester side of a chunked include?: one workgroup per route tile; the tile's chunk in
@@ -2318,16 +2295,13 @@ hipError_t launch_groups_mid(const BfGeom& g, const BfBinPlan& p, const Carve& c
     launch_scan(p, c, s);
     bf_mark(mk, s, "bin_group");
     const uint32_t tiles_per_group = kGroupBlocks * p.tiles_per_block;
-    if (p.with_keys)
-        hipLaunchKernelGGL(bin_mid_kernel<true>, dim3(mid_grid(p.nsup, p.ngroups)), dim3(kTile), 0, s, c.level1,
-                           c.level1_key, c.stab, p.ntiles, p.tile_probes, tiles_per_group, p.nsup, p.ngroups,
-                           p.region_log2, p.rel_log2, c.base, c.cb_base, p.max_chunks, c.tabs, c.level2,
-                           c.level2_key);
-    else
-        hipLaunchKernelGGL(bin_mid_kernel<false>, dim3(mid_grid(p.nsup, p.ngroups)), dim3(kTile), 0, s, c.level1,
-                           c.level1_key, c.stab, p.ntiles, p.tile_probes, tiles_per_group, p.nsup, p.ngroups,
-                           p.region_log2, p.rel_log2, c.base, c.cb_base, p.max_chunks, c.tabs, c.level2,
-                           c.level2_key);
+    auto mid = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(mid_grid(p.nsup, p.ngroups)), dim3(kTile), 0, s, c.level1, c.level1_key, c.stab,
+                           p.ntiles, p.tile_probes, tiles_per_group, p.nsup, p.ngroups, p.region_log2, p.rel_log2,
+                           c.base, c.cb_base, p.max_chunks, c.tabs, c.level2, c.level2_key);
+    };
+    if (p.with_keys) mid(bin_mid_kernel<true>);
+    else mid(bin_mid_kernel<false>);
     bf_mark(mk, s, p.with_keys ? "bin_mid_keys" : "bin_mid");
     return hipGetLastError();
 }
@@ -2339,44 +2313,26 @@ hipError_t launch_partition(const BfGeom& g, const BfBinPlan& p, const Carve& c,
                             BfMarks* mk, bool dig = false) {
     const uint32_t sup_log2 = p.region_log2 + p.rel_log2;
     const bool wide = front_form(g.k) == 2;   // 16 probe slots per lane
+    auto front = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(p.nblocks), dim3(kTile), 0, s, g, keys16, offsets, bias, n, p.tile_keys,
+                           p.tiles_per_block, sup_log2, p.nsup, c.level1, c.level1_key, c.stab, c.gcnt, out8);
+    };
     if (dig) {
         if (p.with_keys) return hipErrorInvalidValue;
         static const bool wide2 = [] {   // A/B: BFHIP_FRONT_WIDE2=0 takes one workgroup per CU
             const char* e = BF_AB_GETENV("BFHIP_FRONT_WIDE2");
             return !(e && e[0] == '0');
         }();
-        if (wide && wide2)
-            hipLaunchKernelGGL(bin_front_wide_dig_kernel, dim3(p.nblocks), dim3(kTile), 0, s, g, keys16, offsets, bias,
-                               n, p.tile_keys, p.tiles_per_block, sup_log2, p.nsup, c.level1, c.level1_key, c.stab,
-                               c.gcnt, out8);
-        else if (wide)
-            hipLaunchKernelGGL((bin_front_wide_kernel<false, true>), dim3(p.nblocks), dim3(kTile), 0, s, g, keys16,
-                               offsets, bias, n, p.tile_keys, p.tiles_per_block, sup_log2, p.nsup, c.level1,
-                               c.level1_key, c.stab, c.gcnt, out8);
-        else
-            hipLaunchKernelGGL(bin_front_kernel<true>, dim3(p.nblocks), dim3(kTile), 0, s, g, keys16, offsets, bias, n,
-                               p.tile_keys, p.tiles_per_block, sup_log2, p.nsup, c.level1, c.level1_key, c.stab,
-                               c.gcnt, out8);
+        if (wide && wide2) front(bin_front_wide_dig_kernel);
+        else if (wide) front(bin_front_wide_kernel<false, true>);
+        else front(bin_front_kernel<true>);
         bf_mark(mk, s, "bin_front_digest");
         return launch_groups_mid(g, p, c, s, mk);
     }
-    if (wide) {
-        if (p.with_keys)
-            hipLaunchKernelGGL(bin_front_wide_kernel<true>, dim3(p.nblocks), dim3(kTile), 0, s, g, keys16, offsets,
-                               bias, n, p.tile_keys, p.tiles_per_block, sup_log2, p.nsup, c.level1, c.level1_key,
-                               c.stab, c.gcnt, out8);
-        else
-            hipLaunchKernelGGL(bin_front_wide_kernel<false>, dim3(p.nblocks), dim3(kTile), 0, s, g, keys16, offsets,
-                               bias, n, p.tile_keys, p.tiles_per_block, sup_log2, p.nsup, c.level1, c.level1_key,
-                               c.stab, c.gcnt, out8);
-    } else if (p.with_keys)
-        hipLaunchKernelGGL(bin_front_keys_kernel, dim3(p.nblocks), dim3(kTile), 0, s, g, keys16, offsets, bias, n,
-                           p.tile_keys, p.tiles_per_block, sup_log2, p.nsup, c.level1, c.level1_key, c.stab, c.gcnt,
-                           out8);
-    else
-        hipLaunchKernelGGL(bin_front_kernel<false>, dim3(p.nblocks), dim3(kTile), 0, s, g, keys16, offsets, bias, n,
-                           p.tile_keys, p.tiles_per_block, sup_log2, p.nsup, c.level1, c.level1_key, c.stab, c.gcnt,
-                           out8);
+    if (wide && p.with_keys) front(bin_front_wide_kernel<true>);
+    else if (wide) front(bin_front_wide_kernel<false>);
+    else if (p.with_keys) front(bin_front_keys_kernel);
+    else front(bin_front_kernel<false>);
     bf_mark(mk, s, p.with_keys ? "bin_front_keys" : "bin_front");
     return launch_groups_mid(g, p, c, s, mk);
 }
@@ -2524,26 +2480,29 @@ hipError_t launch_apply(const BfGeom& g, const BfBinPlan& p, const Carve& c, uin
     const uint64_t nwords = bitset_bytes / 4;
     const uint32_t dense = probe_density(p.probes, p.nbins, p.region_log2);
     const uint32_t pg = apply_pipe_grid();
+    auto pipe = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(std::min<uint32_t>(p.nbins, pg)), dim3(kPipeLanes), 0, s, g.bits, nwords,
+                           p.nbins, c.level2, c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups, p.rel_log2, dense,
+                           any_flag, g.dirty, apply_store_fresh());
+    };
+    auto apply = [&](auto kernel, uint32_t lanes) {
+        hipLaunchKernelGGL(kernel, dim3(p.nbins), dim3(lanes), 0, s, g.bits, nwords, c.level2, c.cb_base, c.cb_start,
+                           c.tabs, p.max_chunks, p.ngroups, p.rel_log2, dense, any_flag, g.dirty, apply_store_fresh(),
+                           apply_xcd_group());
+    };
     if (apply_pipelined(dense, apply_form(dense), p.region_log2, p.nbins, pg)) {
         [[maybe_unused]] static const int pl = [] {
             const char* e = BF_AB_GETENV("BFHIP_APPLY_PIPE_LOADS");
             return e && *e && std::atoi(e) == 4 ? 4 : 8;
         }();
-#define BF_APPLY_PIPE(LD)                                                                                         \
-    hipLaunchKernelGGL((bin_apply_pipe_kernel<19, kPipeLanes, LD>), dim3(std::min<uint32_t>(p.nbins, pg)),         \
-                       dim3(kPipeLanes), 0, s, g.bits, nwords, p.nbins, c.level2, c.cb_base, c.cb_start, c.tabs,   \
-                       p.max_chunks, p.ngroups, p.rel_log2, dense, any_flag, g.dirty, apply_store_fresh())
 #ifdef BFHIP_AB_KNOBS
-        if (pl == 4) BF_APPLY_PIPE(4);
+        if (pl == 4) pipe(bin_apply_pipe_kernel<19, kPipeLanes, 4>);
         else
 #endif
-        BF_APPLY_PIPE(8);
-#undef BF_APPLY_PIPE
-    } else if (p.region_log2 == 18)
-        hipLaunchKernelGGL((bin_apply_kernel<18, kApplyLanes / 2>), dim3(p.nbins), dim3(kApplyLanes / 2), 0, s,
-                           g.bits, nwords, c.level2, c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups,
-                           p.rel_log2, dense, any_flag, g.dirty, apply_store_fresh(), apply_xcd_group());
-    else if (p.region_log2 == 19) {
+        pipe(bin_apply_pipe_kernel<19, kPipeLanes, 8>);
+    } else if (p.region_log2 == 18) {
+        apply(bin_apply_kernel<18, kApplyLanes / 2>, kApplyLanes / 2);
+    } else if (p.region_log2 == 19) {
         // level-2 loads per lane and gather step (region_loads; BFHIP_APPLY_LOADS forces, A/B)
         static const int forced = [] {
             const char* e = BF_AB_GETENV("BFHIP_APPLY_LOADS");
@@ -2551,22 +2510,15 @@ hipError_t launch_apply(const BfGeom& g, const BfBinPlan& p, const Carve& c, uin
             return v == 1 || v == 2 || v == 4 || v == 8 ? v : 0;
         }();
         const int loads = forced ? forced : region_loads(p.probes, p.nbins);
-#define BF_APPLY19(LD)                                                                                          \
-    hipLaunchKernelGGL((bin_apply_kernel<19, kApplyLanes, LD>), dim3(p.nbins), dim3(kApplyLanes), 0, s, g.bits, \
-                       nwords, c.level2, c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups, p.rel_log2, dense, \
-                       any_flag, g.dirty, apply_store_fresh(), apply_xcd_group())
-        if (loads == 2) BF_APPLY19(2);
+        if (loads == 2) apply(bin_apply_kernel<19, kApplyLanes, 2>, kApplyLanes);
 #ifdef BFHIP_AB_KNOBS
-        else if (loads == 1) BF_APPLY19(1);
-        else if (loads == 4) BF_APPLY19(4);
+        else if (loads == 1) apply(bin_apply_kernel<19, kApplyLanes, 1>, kApplyLanes);
+        else if (loads == 4) apply(bin_apply_kernel<19, kApplyLanes, 4>, kApplyLanes);
 #endif
-        else BF_APPLY19(8);
-#undef BF_APPLY19
+        else apply(bin_apply_kernel<19, kApplyLanes, 8>, kApplyLanes);
+    } else {
+        apply(bin_apply_kernel<20, kApplyLanes>, kApplyLanes);
     }
-    else
-        hipLaunchKernelGGL((bin_apply_kernel<20, kApplyLanes>), dim3(p.nbins), dim3(kApplyLanes), 0, s, g.bits,
-                           nwords, c.level2, c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups, p.rel_log2, dense,
-                           any_flag, g.dirty, apply_store_fresh(), apply_xcd_group());
     bf_mark(mk, s, "bin_apply");
     return hipGetLastError();
 }
@@ -2621,14 +2573,12 @@ hipError_t bf_launch_shard_insert_binned(const BfGeom& g, const BfBinPlan& p, ui
     if (w.counts && (w.cap == 0 || w.cap % kTileProbes)) return hipErrorInvalidValue;
     const Carve c = carve(p, scratch);
     const uint32_t sup_log2 = p.region_log2 + p.rel_log2;
-    if (route32)
-        hipLaunchKernelGGL(bin_front_offsets_kernel<uint32_t>, dim3(p.nblocks), dim3(kTile), 0, s,
-                           static_cast<const uint32_t*>(local), count, p.tiles_per_block, sup_log2, p.nsup, c.level1,
-                           c.stab, c.gcnt, bias, w.counts, w.stride, w.cap, g.limit);
-    else
-        hipLaunchKernelGGL(bin_front_offsets_kernel<uint64_t>, dim3(p.nblocks), dim3(kTile), 0, s,
-                           static_cast<const uint64_t*>(local), count, p.tiles_per_block, sup_log2, p.nsup, c.level1,
-                           c.stab, c.gcnt, bias, w.counts, w.stride, w.cap, g.limit);
+    auto front = [&](auto kernel, auto* offs) {
+        hipLaunchKernelGGL(kernel, dim3(p.nblocks), dim3(kTile), 0, s, offs, count, p.tiles_per_block, sup_log2, p.nsup,
+                           c.level1, c.stab, c.gcnt, bias, w.counts, w.stride, w.cap, g.limit);
+    };
+    if (route32) front(bin_front_offsets_kernel<uint32_t>, static_cast<const uint32_t*>(local));
+    else front(bin_front_offsets_kernel<uint64_t>, static_cast<const uint64_t*>(local));
     bf_mark(mk, s, "bin_front_offsets");
     hipError_t e = launch_groups_mid(g, p, c, s, mk);
     if (e != hipSuccess) return e;
@@ -2640,18 +2590,13 @@ namespace {
 hipError_t launch_test(const BfGeom& g, const BfBinPlan& p, const Carve& c, uint64_t bitset_bytes, uint8_t* out8,
                        hipStream_t s, BfMarks* mk) {
     const uint64_t nwords = bitset_bytes / 4;
-    if (p.region_log2 == 18)
-        hipLaunchKernelGGL((bin_test_kernel<18, kApplyLanes / 2>), dim3(p.nbins), dim3(kApplyLanes / 2), 0, s,
-                           g.bits, nwords, c.level2, c.level2_key, c.cb_base, c.cb_start, c.tabs, p.max_chunks,
-                           p.ngroups, p.rel_log2, out8);
-    else if (p.region_log2 == 19)
-        hipLaunchKernelGGL((bin_test_kernel<19, kApplyLanes>), dim3(p.nbins), dim3(kApplyLanes), 0, s, g.bits,
-                           nwords, c.level2, c.level2_key, c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups,
-                           p.rel_log2, out8);
-    else
-        hipLaunchKernelGGL((bin_test_kernel<20, kApplyLanes>), dim3(p.nbins), dim3(kApplyLanes), 0, s, g.bits,
-                           nwords, c.level2, c.level2_key, c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups,
-                           p.rel_log2, out8);
+    auto test = [&](auto kernel, uint32_t lanes) {
+        hipLaunchKernelGGL(kernel, dim3(p.nbins), dim3(lanes), 0, s, g.bits, nwords, c.level2, c.level2_key, c.cb_base,
+                           c.cb_start, c.tabs, p.max_chunks, p.ngroups, p.rel_log2, out8);
+    };
+    if (p.region_log2 == 18) test(bin_test_kernel<18, kApplyLanes / 2>, kApplyLanes / 2);
+    else if (p.region_log2 == 19) test(bin_test_kernel<19, kApplyLanes>, kApplyLanes);
+    else test(bin_test_kernel<20, kApplyLanes>, kApplyLanes);
     bf_mark(mk, s, "bin_test");
     return hipGetLastError();
 }
@@ -2671,14 +2616,12 @@ hipError_t bf_launch_shard_test_binned(const BfGeom& g, const BfBinPlan& p, uint
     const uint32_t sup_log2 = p.region_log2 + p.rel_log2;
     hipError_t e = hipMemsetAsync(out8, 1, count, s);
     if (e != hipSuccess) return e;
-    if (route32)
-        hipLaunchKernelGGL(bin_front_offsets_keys_kernel<uint32_t>, dim3(p.nblocks), dim3(kTile), 0, s,
-                           static_cast<const uint32_t*>(local), count, p.tiles_per_block, sup_log2, p.nsup, c.level1,
-                           c.level1_key, c.stab, c.gcnt, bias, w.counts, w.stride, w.cap, g.limit, out8);
-    else
-        hipLaunchKernelGGL(bin_front_offsets_keys_kernel<uint64_t>, dim3(p.nblocks), dim3(kTile), 0, s,
-                           static_cast<const uint64_t*>(local), count, p.tiles_per_block, sup_log2, p.nsup, c.level1,
-                           c.level1_key, c.stab, c.gcnt, bias, w.counts, w.stride, w.cap, g.limit, out8);
+    auto front = [&](auto kernel, auto* offs) {
+        hipLaunchKernelGGL(kernel, dim3(p.nblocks), dim3(kTile), 0, s, offs, count, p.tiles_per_block, sup_log2, p.nsup,
+                           c.level1, c.level1_key, c.stab, c.gcnt, bias, w.counts, w.stride, w.cap, g.limit, out8);
+    };
+    if (route32) front(bin_front_offsets_keys_kernel<uint32_t>, static_cast<const uint32_t*>(local));
+    else front(bin_front_offsets_keys_kernel<uint64_t>, static_cast<const uint64_t*>(local));
     bf_mark(mk, s, "bin_front_offsets_keys");
     if ((e = launch_groups_mid(g, p, c, s, mk)) != hipSuccess) return e;
     return launch_test(g, p, c, bitset_bytes, out8, s, mk);
@@ -3023,23 +2966,18 @@ hipError_t bf_launch_shard_test_chunks(const BfGeom& g, const BfBinPlan& p, uint
             const char* e = BF_AB_GETENV("BFHIP_L2_LOADS");
             return e && *e ? std::atoi(e) : kL2Loads;
         }();
-        if (side.n)
-            hipLaunchKernelGGL(chunk_test_l2_kernel<true>, dim3(grid), dim3(kL2Lanes), 0, s, ci, g.bits, p.nsup,
-                               p.ngroups, parts, c.gsum, c.runs, c.istart, out8, side);
+        auto test = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kL2Lanes), 0, s, ci, g.bits, p.nsup, p.ngroups, parts, c.gsum,
+                               c.runs, c.istart, out8, side);
+        };
+        if (side.n) test(chunk_test_l2_kernel<true>);
 #ifdef BFHIP_AB_KNOBS
-        else if (walk && l2_loads == 16)   // (A/B: BFHIP_L2_LOADS, entries per lane in flight)
-            hipLaunchKernelGGL((chunk_test_l2_kernel<false, true, 16>), dim3(grid), dim3(kL2Lanes), 0, s, ci,
-                               g.bits, p.nsup, p.ngroups, parts, c.gsum, c.runs, c.istart, out8, side);
-        else if (walk && l2_loads == 4)
-            hipLaunchKernelGGL((chunk_test_l2_kernel<false, true, 4>), dim3(grid), dim3(kL2Lanes), 0, s, ci,
-                               g.bits, p.nsup, p.ngroups, parts, c.gsum, c.runs, c.istart, out8, side);
-        else if (!walk)
-            hipLaunchKernelGGL((chunk_test_l2_kernel<false, false>), dim3(grid), dim3(kL2Lanes), 0, s, ci, g.bits,
-                               p.nsup, p.ngroups, parts, c.gsum, c.runs, c.istart, out8, side);
+        // (A/B: BFHIP_L2_LOADS, entries per lane in flight)
+        else if (walk && l2_loads == 16) test(chunk_test_l2_kernel<false, true, 16>);
+        else if (walk && l2_loads == 4) test(chunk_test_l2_kernel<false, true, 4>);
+        else if (!walk) test(chunk_test_l2_kernel<false, false>);
 #endif
-        else
-            hipLaunchKernelGGL((chunk_test_l2_kernel<false, true>), dim3(grid), dim3(kL2Lanes), 0, s, ci, g.bits,
-                               p.nsup, p.ngroups, parts, c.gsum, c.runs, c.istart, out8, side);
+        else test(chunk_test_l2_kernel<false, true>);
         bf_mark(mk, s, side.n ? "test_l2_hash" : "test_l2");
         return hipGetLastError();
     }
@@ -3067,18 +3005,13 @@ hipError_t bf_launch_shard_test_chunks_packed(const BfGeom& g, const BfBinPlan& 
     if (e != hipSuccess) return e;
     if ((e = launch_chunk_mid(p, c, ci, nullptr, s, mk)) != hipSuccess) return e;
     const uint64_t nwords = bitset_bytes / 4;
-    if (p.region_log2 == 18)
-        hipLaunchKernelGGL((bin_test_kernel<18, kApplyLanes / 2, true>), dim3(p.nbins), dim3(kApplyLanes / 2), 0, s,
-                           g.bits, nwords, c.level2, c.level2_key, c.cb_base, c.cb_start, c.tabs, p.max_chunks,
-                           p.ngroups, p.rel_log2, c.ans2);
-    else if (p.region_log2 == 19)
-        hipLaunchKernelGGL((bin_test_kernel<19, kApplyLanes, true>), dim3(p.nbins), dim3(kApplyLanes), 0, s, g.bits,
-                           nwords, c.level2, c.level2_key, c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups,
-                           p.rel_log2, c.ans2);
-    else
-        hipLaunchKernelGGL((bin_test_kernel<20, kApplyLanes, true>), dim3(p.nbins), dim3(kApplyLanes), 0, s, g.bits,
-                           nwords, c.level2, c.level2_key, c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups,
-                           p.rel_log2, c.ans2);
+    auto test = [&](auto kernel, uint32_t lanes) {
+        hipLaunchKernelGGL(kernel, dim3(p.nbins), dim3(lanes), 0, s, g.bits, nwords, c.level2, c.level2_key, c.cb_base,
+                           c.cb_start, c.tabs, p.max_chunks, p.ngroups, p.rel_log2, c.ans2);
+    };
+    if (p.region_log2 == 18) test(bin_test_kernel<18, kApplyLanes / 2, true>, kApplyLanes / 2);
+    else if (p.region_log2 == 19) test(bin_test_kernel<19, kApplyLanes, true>, kApplyLanes);
+    else test(bin_test_kernel<20, kApplyLanes, true>, kApplyLanes);
     bf_mark(mk, s, "bin_test_l2order");
     hipLaunchKernelGGL(chunk_unsort_kernel, dim3(p.ngroups, ci.nh), dim3(1024), 0, s, ci, p.ngroups, p.nsup, c.base,
                        c.level2_key, c.ans2, packed, cap8);
@@ -3689,277 +3622,6 @@ void sets_apply_encode_kernel(uint32_t* __restrict__ bits, uint64_t nwords, cons
                                             sb_first, cap_words, 0u, s_mask4, s_lows, s_tabs.w);
 }
 
-#ifdef BFHIP_AB_KNOBS
-// (A/B only, BFHIP_SETS_PIPE=1; measured slower, DESIGN §6f: 5.06 vs 4.58 ms at 10B x 8, 0.61
-// vs 0.53 ms at the north star x 2 — one region per CU at a time loses to two one-shot
-// workgroups per CU, whose decodes overlap each other's barrier and scan latency.)
-// sets_apply_kernel, persistent and software-pipelined (one 1024-lane workgroup per CU walking
-// regions r, r + G, ...), for batches dense enough to rewrite every region (VERDICT r04 item
-// 4).  The one-shot kernel pays, per region, two dependent round trips (the per-source headers,
-// then the sets' words) before it can decode, and at the 10B filter decodes every offset's low
-// bits with a dependent global load (16 KB of them do not fit its 15 KB stage at two workgroups
-// per CU).  Here, while region r is decoded from LDS, region r + G's set words (the first UPL
-// upper-bitmap words and up to LPL low-bit words per lane) and its 64 KB of bitset vectors are
-// already in flight in registers, and r + 2G's headers too; r's low bits were staged into LDS
-// (LPL x LANES words, 24 KB) at the top of its iteration.  Region r + G's source tables (place,
-// header, the three per-source prefixes) are built into the second of two LDS table buffers.
-// The prefetch loads are unconditional (a clamped stand-in address past the data), so the
-// compiler's in-order vmcnt waits leave them outstanding while r decodes.  Words beyond the
-// prefetch (more than UPL x LANES upper words, or low bits past the stage) and bitmap sets are
-// read on the spot, as the one-shot kernel does.  Results are the one-shot kernel's, bit for
-// bit (tests/test_gpu_region_sets.py runs both).
-template <uint32_t RLOG2, uint32_t LANES, uint32_t UPL, uint32_t LPL>
-__global__ __launch_bounds__(LANES) __attribute__((amdgpu_waves_per_eu(4, 4))) void sets_apply_pipe_kernel(
-    uint32_t* __restrict__ bits, uint64_t nwords, const uint32_t* __restrict__ sets, uint64_t stride_words,
-    uint32_t nsrc, uint32_t nbins, uint32_t dense, uint32_t* __restrict__ any_flag, uint8_t* __restrict__ dirty,
-    uint32_t store_fresh, uint32_t* __restrict__ status) {
-    constexpr uint32_t kVec = 1u << (RLOG2 - 7);
-    constexpr uint32_t kPer = kVec / LANES;
-    constexpr uint32_t U = 1u << RLOG2, NW = U / 32;
-    constexpr uint32_t kStage = LPL * LANES;
-    static_assert(kPer * LANES == kVec, "region must tile the workgroup");
-    __shared__ uint4 s_mask4[kVec];
-    __shared__ uint32_t s_lows[kStage + 1];
-    __shared__ uint32_t s_w[16];
-    __shared__ uint32_t s_st[2][kMaxSetSrc], s_hdr[2][kMaxSetSrc];
-    __shared__ uint32_t s_uw0[2][kMaxSetSrc + 1], s_np[2][kMaxSetSrc + 1], s_lw0[2][kMaxSetSrc + 1];
-    __shared__ uint32_t s_ok;
-    uint32_t* s_mask = reinterpret_cast<uint32_t*>(s_mask4);
-    const uint32_t t = threadIdx.x;
-    const uint32_t G = gridDim.x;
-    const uint64_t nvec = nwords / 4;
-    uint4* gv = reinterpret_cast<uint4*>(bits);
-    if (blockIdx.x >= nbins) return;   // workgroup-uniform
-    const uint32_t last = blockIdx.x + (nbins - 1 - blockIdx.x) / G * G;
-    auto clampr = [&](uint32_t q) { return q < last ? q : last; };
-
-    // which sources' buffers match this filter (one header check per workgroup)
-    if (t == 0) s_ok = 0;
-    for (uint32_t v = t; v < kVec; v += LANES) s_mask4[v] = make_uint4(0, 0, 0, 0);
-    __syncthreads();
-    if (t < nsrc) {
-        const uint32_t* S = sets + (uint64_t)t * stride_words;
-        const bool ok = S[0] == kSetsMagic && S[1] == RLOG2 && S[2] == nbins && S[3] >= sets_first_word(nbins) &&
-                        S[3] <= stride_words;
-        if (ok) atomicOr(&s_ok, 1u << t);
-        else if (status) atomicOr(status, 1u);
-    }
-    __syncthreads();
-    const uint32_t okmask = s_ok;
-    const bool my_ok = t < nsrc && ((okmask >> t) & 1u);
-    const uint32_t* mine = sets + (uint64_t)(t < nsrc ? t : 0) * stride_words;
-
-    // region q's place and header of source t (lanes t < nsrc)
-    auto load_hdr = [&](uint32_t q, uint32_t& st, uint32_t& hdr) {
-        st = hdr = 0;
-        if (my_ok) {
-            st = mine[kSetsHdr + q];
-            hdr = mine[kSetsHdr + nbins + q];
-        }
-    };
-    // the tables of a region into buffer bi: damaged entries dropped (and flagged), the
-    // per-source prefixes of upper words, offsets and low-bit words.  Contains a barrier.
-    auto tables = [&](uint32_t bi, uint32_t st, uint32_t hdr) {
-        if (t < 64) {
-            if (t < nsrc && st) {
-                const uint32_t n = hdr & 0xFFFFFFu, l = hdr >> 24;
-                const bool shape = n && n <= U && (l == kSetsBitmap || (l >= 1u && l <= RLOG2));   // (EF: l >= 1)
-                const uint64_t need = !shape ? 0 : 1ull + (l == kSetsBitmap ? NW : (n * l + 31u) / 32u +
-                                                                                 (n + (U >> l) + 31u) / 32u);
-                if (!shape || (uint64_t)st + need > stride_words) {
-                    st = hdr = 0;
-                    if (status) atomicOr(status, 1u);
-                }
-            }
-            if (t >= nsrc) st = hdr = 0;
-            const uint32_t n = hdr & 0xFFFFFFu, l = hdr >> 24;
-            const bool ef = st && l != kSetsBitmap;
-            const uint32_t ua = ef ? (n + (U >> l) + 31u) / 32u : 0u, nn = ef ? n : 0u,
-                           ll = ef ? (n * l + 31u) / 32u : 0u;
-            const uint32_t ia = wave_incl_scan(ua), in = wave_incl_scan(nn), il = wave_incl_scan(ll);
-            if (t < nsrc) {
-                s_st[bi][t] = st;
-                s_hdr[bi][t] = hdr;
-            }
-            if (t <= nsrc) {
-                s_uw0[bi][t] = ia - ua;
-                s_np[bi][t] = in - nn;
-                s_lw0[bi][t] = il - ll;
-            }
-        }
-        __syncthreads();
-    };
-    // the last source whose start in table `starts` is <= q (four dependent LDS reads)
-    auto source_of = [&](const uint32_t* starts, uint32_t q) {
-        uint32_t s = 0;
-#pragma unroll
-        for (uint32_t stp = kMaxSetSrc / 2; stp; stp >>= 1)
-            if (s + stp < nsrc && starts[s + stp] <= q) s += stp;
-        return s;
-    };
-    // address of upper-bitmap word g / low-bit word q of the region in table bi (a stand-in,
-    // the buffer's first word, past the region's words: every prefetch issues)
-    auto upper_addr = [&](uint32_t bi, uint32_t g) -> const uint32_t* {
-        if (g >= s_uw0[bi][nsrc]) return sets;
-        const uint32_t s = source_of(s_uw0[bi], g);
-        const uint32_t n = s_hdr[bi][s] & 0xFFFFFFu, l = s_hdr[bi][s] >> 24;
-        return sets + (uint64_t)s * stride_words + s_st[bi][s] + 1 + (n * l + 31u) / 32u + (g - s_uw0[bi][s]);
-    };
-    auto lows_addr = [&](uint32_t bi, uint32_t q) -> const uint32_t* {
-        if (q >= s_lw0[bi][nsrc]) return sets;
-        const uint32_t s = source_of(s_lw0[bi], q);
-        return sets + (uint64_t)s * stride_words + s_st[bi][s] + 1 + (q - s_lw0[bi][s]);
-    };
-    auto load_words = [&](uint32_t bi, uint32_t* uw, uint32_t* lo) {
-#pragma unroll
-        for (uint32_t p = 0; p < UPL; ++p) uw[p] = *upper_addr(bi, p * LANES + t);
-#pragma unroll
-        for (uint32_t j = 0; j < LPL; ++j) lo[j] = *lows_addr(bi, j * LANES + t);
-    };
-    auto load_vecs = [&](uint32_t q, uint4* vo) {
-        const uint64_t v0 = (uint64_t)q * kVec;
-#pragma unroll
-        for (uint32_t c = 0; c < kPer; ++c) {
-            const uint64_t v = v0 + c * LANES + t;
-            vo[c] = apply_load(gv + (v < nvec ? v : nvec - 1));
-        }
-    };
-
-    uint32_t fresh = 0;
-    // Region r (tables in buffer bi, its vectors cur, words uw / lo in registers), r + G's
-    // headers (hst, hhd) loaded.  Issues r + G's words / vectors into (nuw, nlo, nxt) and r + 2G's
-    // headers into (nst, nhd).
-    auto region = [&](uint32_t r, uint32_t bi, const uint4* cur, const uint32_t* uw, const uint32_t* lo,
-                      uint32_t hst, uint32_t hhd, uint4* nxt, uint32_t* nuw, uint32_t* nlo, uint32_t& nst,
-                      uint32_t& nhd) {
-        // r's low bits into the stage (the previous region's decode ended on a barrier).  The
-        // workgroup-uniform values read from LDS go through readfirstlane, so that their branches
-        // are scalar: a wait inside a branch the compiler must treat as divergent runs on every
-        // path, and a vmcnt(0) there would wait for r + G's prefetch
-        const uint32_t TL = __builtin_amdgcn_readfirstlane(s_lw0[bi][nsrc]);
-        const bool staged = TL <= kStage;   // workgroup-uniform
-        if (staged) {
-#pragma unroll
-            for (uint32_t j = 0; j < LPL; ++j) s_lows[j * LANES + t] = lo[j];
-            if (t == 0) s_lows[TL] = 0;   // read past the last source's lows, masked off
-        }
-        // r + G's tables (their barrier also publishes the stage), then its prefetches
-        const uint32_t rn = clampr(r + G);
-        tables(bi ^ 1u, hst, hhd);
-        load_hdr(clampr(r + 2 * G), nst, nhd);
-        load_words(bi ^ 1u, nuw, nlo);
-        load_vecs(rn, nxt);
-        // decode r: bitmap sets word by word (rare: read on the spot)
-        for (uint32_t s = 0; s < nsrc; ++s) {
-            const uint32_t sst = __builtin_amdgcn_readfirstlane(s_st[bi][s]);
-            const uint32_t shd = __builtin_amdgcn_readfirstlane(s_hdr[bi][s]);
-            if (!sst || (shd >> 24) != kSetsBitmap) continue;   // workgroup-uniform
-            const uint32_t* B = sets + (uint64_t)s * stride_words + sst + 1;
-            for (uint32_t v = t; v < NW; v += LANES) {
-                const uint32_t x = B[v];
-                if (x) atomicOr(s_mask + v, x);
-            }
-            __builtin_amdgcn_s_waitcnt(kWaitVm0);
-        }
-        // Elias-Fano sets: one pass of LANES upper words at a time over all sources.  The first
-        // UPL passes use the prefetched words, as straight-line code: in a loop the compiler's
-        // wait for those registers becomes vmcnt(0), which would also wait for r + G's prefetch.
-        const uint32_t TW = __builtin_amdgcn_readfirstlane(s_uw0[bi][nsrc]);
-        uint32_t carry = 0;
-        // (staged is a compile-time branch: a run-time select between the LDS stage and global
-        // memory would be a flat load, whose wait is vmcnt(0) as well)
-        auto pass = [&](auto stg, uint32_t g, uint32_t word) {   // contains barriers (the scan)
-            constexpr bool kStaged = decltype(stg)::value;
-            uint32_t tot;
-            const uint32_t pre = block_excl_scan(__popc(word), s_w, &tot);
-            if (word) {
-                const uint32_t s = source_of(s_uw0[bi], g);
-                const uint32_t n = s_hdr[bi][s] & 0xFFFFFFu, l = s_hdr[bi][s] >> 24;
-                const uint32_t* lows = sets + (uint64_t)s * stride_words + s_st[bi][s] + 1;
-                const uint32_t* slows = s_lows + s_lw0[bi][s];
-                const uint32_t lmask = (1u << l) - 1u;
-                uint32_t i = carry + pre - s_np[bi][s];   // rank of this word's first offset in its set
-                const uint32_t p0 = (g - s_uw0[bi][s]) * 32u;
-                const uint32_t lim = l ? (n * l + 31u) / 32u - 1u : 0u;   // last low-bits word
-                while (word) {
-                    const uint32_t pp = p0 + (uint32_t)__builtin_ctz(word);
-                    word &= word - 1u;
-                    uint32_t lo_ = 0;
-                    if (l) {
-                        const uint32_t bp = i * l, wi = bp >> 5;
-                        uint32_t a, b;
-                        if constexpr (kStaged) {   // (a damaged set's ranks can pass n: reads stay inside its lows)
-                            a = slows[min(wi, lim)];
-                            b = slows[min(wi, lim) + 1u];
-                        } else {
-                            a = lows[min(wi, lim)];
-                            b = lows[min(wi + 1u, lim)];
-                        }
-                        lo_ = (uint32_t)(((uint64_t)b << 32 | a) >> (bp & 31u)) & lmask;
-                    }
-                    const uint32_t x = ((pp - i) << l) | lo_;
-                    if (x < U) atomicOr(s_mask + (x >> 5), 1u << ((x ^ 7u) & 31u));
-                    ++i;
-                }
-            }
-            carry += tot;
-        };
-        if (staged) {
-#pragma unroll
-            for (uint32_t p = 0; p < UPL; ++p)   // workgroup-uniform tests
-                if (p * LANES < TW) pass(std::true_type{}, p * LANES + t, p * LANES + t < TW ? uw[p] : 0u);
-        } else {   // (low bits past the stage: read on the spot, each read waited out)
-#pragma unroll
-            for (uint32_t p = 0; p < UPL; ++p)
-                if (p * LANES < TW) pass(std::false_type{}, p * LANES + t, p * LANES + t < TW ? uw[p] : 0u);
-        }
-        for (uint32_t g0 = UPL * LANES; g0 < TW; g0 += LANES) {   // more upper words: read on the spot
-            const uint32_t g = g0 + t;
-            const uint32_t word = g < TW ? *upper_addr(bi, g) : 0u;
-            if (staged) pass(std::true_type{}, g, word);
-            else pass(std::false_type{}, g, word);
-            __builtin_amdgcn_s_waitcnt(kWaitVm0);   // (the rare path ends on a full wait, as the main path may assume)
-        }
-        __syncthreads();   // the image is complete
-        const uint64_t v0 = (uint64_t)r * kVec;
-#pragma unroll
-        for (uint32_t c = 0; c < kPer; ++c) {
-            const uint32_t v = c * LANES + t;
-            const uint4 m = s_mask4[v];
-            s_mask4[v] = make_uint4(0, 0, 0, 0);
-            if (v0 + v < nvec && (dense == 2 || (m.x | m.y | m.z | m.w))) {
-                const uint32_t fr = (m.x & ~cur[c].x) | (m.y & ~cur[c].y) | (m.z & ~cur[c].z) | (m.w & ~cur[c].w);
-                fresh |= fr;
-                if (store_fresh && dense != 2 && !fr) continue;
-                apply_store(gv + v0 + v, make_uint4(cur[c].x | m.x, cur[c].y | m.y, cur[c].z | m.z, cur[c].w | m.w));
-                if (dirty && fr) dirty[((v0 + v) * 128) >> kDirtyShiftBits] = 1;
-            }
-        }
-        __syncthreads();   // every lane is past its reads of the stage and of table bi
-    };
-
-    // prologue: region blockIdx.x's tables, words and vectors; the next region's headers
-    uint32_t r = blockIdx.x;
-    uint4 bufA[kPer], bufB[kPer];
-    uint32_t uwA[UPL], uwB[UPL], loA[LPL], loB[LPL];
-    uint32_t stA, hdA, stB, hdB;
-    {
-        uint32_t st0, hd0;
-        load_hdr(r, st0, hd0);
-        tables(0u, st0, hd0);
-        load_hdr(clampr(r + G), stA, hdA);
-        load_words(0u, uwA, loA);
-        load_vecs(r, bufA);
-    }
-    for (;; r += 2 * G) {
-        region(r, 0u, bufA, uwA, loA, stA, hdA, bufB, uwB, loB, stB, hdB);
-        if (r + G >= nbins) break;
-        region(r + G, 1u, bufB, uwB, loB, stB, hdB, bufA, uwA, loA, stA, hdA);
-        if (r + 2 * G >= nbins) break;
-    }
-    if (any_flag) report_any_new(any_flag, fresh != 0);
-}
-#endif  // BFHIP_AB_KNOBS
 }  // namespace
 
 namespace {
@@ -4090,27 +3752,9 @@ hipError_t bf_launch_insert_sets(const BfGeom& g, uint64_t bitset_bytes, uint32_
         const char* e = BF_AB_GETENV("BFHIP_SETS_XG");
         return e && *e ? (uint32_t)std::strtoul(e, nullptr, 10) : 2u;
     }();
-#ifdef BFHIP_AB_KNOBS
-    // (A/B: BFHIP_SETS_PIPE=1 takes the persistent pipelined form for dense batches at 2^19-bit
-    // regions with many regions per workgroup; measured slower, kept for the record)
-    static const uint32_t pg = apply_pipe_grid();
-    static const bool pipe_on = [] {
-        const char* e = BF_AB_GETENV("BFHIP_SETS_PIPE");
-        return e && e[0] == '1';
-    }();
-    const bool pipe = pipe_on && apply_pipelined(dense, 1u, region_log2, nbins, pg);
-#endif
     for (uint32_t s0 = 0; s0 < nsrc; s0 += kMaxSetSrc) {
         const uint32_t ns = std::min<uint32_t>(kMaxSetSrc, nsrc - s0);
         const uint32_t* src = sets + (uint64_t)s0 * stride_words;
-#ifdef BFHIP_AB_KNOBS
-        if (pipe) {
-            hipLaunchKernelGGL((sets_apply_pipe_kernel<19, kPipeLanes, 2, 5>), dim3(std::min<uint32_t>(nbins, pg)),
-                               dim3(kPipeLanes), 0, s, g.bits, nwords, src, stride_words, ns, nbins, dense, any_flag,
-                               g.dirty, apply_store_fresh(), status);
-            continue;
-        }
-#endif
 #define BF_SETS_APPLY(RL, LN, ST)                                                                              \
     hipLaunchKernelGGL((sets_apply_kernel<RL, LN, ST>), dim3(nbins), dim3(LN), 0, s, g.bits, nwords, src,       \
                        stride_words, ns, nbins, dense, any_flag, g.dirty, apply_store_fresh(), status, sets_xg)

@@ -367,3 +367,33 @@ def test_per_region_kernels_run_table_passes(pkg, oracle, monkeypatch, keys):
         got = include_dev(f, Dev(probe))
     np.testing.assert_array_equal(got, oracle.include_many(want.bits, m, k, probe[0], probe[1]))
     assert got[:n].all()
+
+
+def test_mid_window_of_three_blocks(pkg, oracle, monkeypatch):
+    """One (superbin, group) window of three chunk blocks with a short last one, through the
+    block loop the two bin_mid kernels share: 4000 keys at k = 6 on a 2^19-bit filter (one region,
+    so one superbin) are 24,000 probes in one group (two front tiles of 2048 keys), so the window
+    is cut into blocks of 8192, 8192 and 7616.  Part 0 of the window's two workgroups sorts
+    one block (no prefetch), part 1 sorts two (the prefetch-and-copy iteration, then the short
+    block).  Insert runs bin_mid_kernel<false>, the forced binned include? bin_mid_kernel<true>
+    with the key indices riding along."""
+    monkeypatch.setenv("BFHIP_INSERT_BINNED", "1")
+    monkeypatch.setenv("BFHIP_INCLUDE_BINNED", "1")
+    monkeypatch.delenv("BFHIP_BIN_REGION_LOG2", raising=False)
+    m, k, n = 2**19, 6, 4000
+    assert (n * k - 1) // 8192 + 1 == 3 and n * k - 2 * 8192 == 7616
+    rng = np.random.default_rng(0xD15E + 30)
+    batch = rand_keys(rng, n)
+    # include?: 2000 members and 2000 other keys, again 24,000 probes in a three-block window
+    probe = cat((batch[0], batch[1][:2001]), rand_keys(rng, 2000))
+    want = Ref(oracle, m, k, batch)
+    with pkg.Filter(m, k, device=0) as f:
+        det = f.insert_plan_detail(n)
+        want_plan = dict(planned=1, binned=1, passes=1, region_log2=19, regions=1, superbins=1, groups=1, tiles=2)
+        assert {key: det[key] for key in want_plan} == want_plan, det
+        assert insert_dev(f, Dev(batch)) is True
+        same_string(f.export_redis(), want.string)
+        assert insert_dev(f, Dev(batch)) is False
+        got = include_dev(f, Dev(probe))
+    np.testing.assert_array_equal(got, oracle.include_many(want.bits, m, k, probe[0], probe[1]))
+    assert got[:2000].all() and not got[2000:].all()

@@ -233,6 +233,10 @@ def check_chunk_route(oracle, D, m, k, P, b, nh, cap, tiles, dbytes, S, send, sl
       for o in ("direct", "sorted", "l2")],
     (191701167547, 13, 4, 20, "l2"),
     (3834023350947, 13, 8, 20, "sorted"),   # 200B x8: nh = 2
+    # one shard of one region: its 36,000 probes are ONE (superbin, group) window of five blocks with
+    # a short last one, so bin_mid_chunks_kernel's two parts run the shared block loop over 2 and 3
+    # blocks (prefetch-and-copy iterations; insert without keys, the packed test with them)
+    (2**19, 6, 1, 19, "sorted"),
 ])
 def test_chunked_windows(pkg, oracle, monkeypatch, m, k, P, b, owner):
     """bf_route_chunks_dev + the owner ops over chunked windows + bf_combine_chunks_packed_dev,
@@ -264,6 +268,10 @@ def test_chunked_windows(pkg, oracle, monkeypatch, m, k, P, b, owner):
     assert dbytes == -(-(claim_off + 8) // 16) * 16
     tile_keys = 2048 if k <= 6 else 1024
     assert tiles == -(-n // tile_keys)
+    if m == 2**19:   # the one-window row: one owner, one superbin (S from the library), one chunk group
+        assert P == 1 and nh == 1 and S == 1 and tiles == 3 <= 1024
+        assert n * k == 36000 and -(-n * k // 8192) == 5 and n * k - 4 * 8192 == 3232   # blocks: 4 full, 1 short
+        assert (5 * 1 // 2, 5 - 5 * 1 // 2) == (2, 3)   # the two parts' shares of the five blocks
     A = 12288
     cap = -(-min(n * k, n * k // P + n * k // (8 * P) + 4096) // A) * A
     rng = np.random.default_rng(23)
@@ -562,3 +570,154 @@ def test_route32_needs_small_shards(pkg):
     f = pkg.Filter(9585058377, 6, shard_count=4, shard_index=1, flags=pkg._lib.BF_FLAG_ROUTE32)
     assert f.route32 and f.local_bits <= 1 << 32
     f.close()
+
+
+def _chunk_dirs(dirb, nwin, dbytes, tiles, S):
+    """Per window: start[tiles], the run lengths tab[S][tiles], the rank table and the claim word."""
+    rank_off = 4 * tiles + 2 * (S + 1) * tiles
+    claim_off = -(-(rank_off + 2 * tiles) // 8) * 8
+    d = dirb.cpu().numpy()
+    out = []
+    for w in range(nwin):
+        dw = d[w * dbytes:(w + 1) * dbytes]
+        start = dw[: 4 * tiles].view(np.uint32).astype(np.int64)
+        length = dw[4 * tiles: rank_off].view(np.uint16).reshape(S + 1, tiles)[S].astype(np.int64)
+        rank = dw[rank_off: rank_off + 2 * tiles].view(np.uint16).astype(np.int64)
+        claim = int(dw[claim_off: claim_off + 8].view(np.uint64)[0])
+        out.append((start, length, rank, claim >> 40, claim & ((1 << 40) - 1)))
+    return out
+
+
+# two route tiles, the second holding one key: 2049 keys at k = 6 (2048-key tiles, the sorted-offset
+# route) and 1025 at k = 13 (1024-key tiles, route_chunks_idx_kernel: HASH from keys, plain from words)
+@pytest.mark.parametrize("m,k,n", [(95851, 6, 2049), (1000003, 13, 1025)])
+def test_chunk_claims_second_tile(pkg, oracle, monkeypatch, m, k, n):
+    """The window claim of the chunked routes at its smallest: P = 2 and two route tiles, so in every
+    window the second claim has rank 1 and a non-zero place (the first run's length).  Rank 0 routes
+    from keys, rank 1 from SHA-1 words; each window and its directory are checked against the oracle
+    (check_chunk_route), then the owners' shards against the oracle's Redis string and the requesters'
+    include? answers against the oracle's."""
+    import torch
+    monkeypatch.setenv("BFHIP_INSERT_BINNED", "1")
+    monkeypatch.setenv("BFHIP_SHARD_TEST_BINNED", "1")
+    monkeypatch.setenv("BFHIP_CHUNK_TEST_L2", "0")
+    D, P, b = pkg.distributed, 2, 10
+    dev = torch.device("cuda", 0)
+    shards = [D.HipEngine(m, k, P, s, b, dev) for s in range(P)]
+    nh = shards[0].nh
+    assert nh == 1
+    tiles, dbytes = shards[0].chunk_info(n)
+    assert tiles == 2
+    S = shards[0].filter.route_chunk_info(n)[2]
+    cap = 12288
+    rng = np.random.default_rng(29)
+    per_rank = [["q%d-%d" % (r, int(v)) for v in rng.integers(0, 10**12, n)] for r in range(P)]
+
+    def route(r, keys):
+        kb, ko, nn, buf, offs = dev_batch(pkg, torch, keys)
+        if r:
+            out = shards[r].route_chunks(shards[r].hash_keys(kb, ko, nn), None, nn, cap, tiles, dbytes)
+        else:
+            out = shards[r].route_chunks(kb, ko, nn, cap, tiles, dbytes)
+        torch.cuda.synchronize()
+        check_chunk_route(oracle, D, m, k, P, b, nh, cap, tiles, dbytes, S, *out, buf, offs)
+        return out + (buf, offs)
+
+    def deliver(routed, o):
+        recv = torch.cat([routed[src][0][o * cap:(o + 1) * cap] for src in range(P)])
+        rdir = torch.cat([routed[src][3][o * dbytes:(o + 1) * dbytes] for src in range(P)])
+        rmsg = torch.zeros(P, 2, dtype=torch.int64, device=dev)
+        for src in range(P):
+            rmsg[src, 0] = routed[src][2][o]
+        return recv, rdir, rmsg
+
+    ins = [route(r, per_rank[r]) for r in range(P)]
+    seen_second = 0
+    for r in range(P):
+        for start, length, rank, nclaim, total in _chunk_dirs(ins[r][3], P, dbytes, tiles, S):
+            assert total == int(length.sum()) <= cap
+            if nclaim == 2:   # the one-key tile has a probe in this window
+                first, second = rank[0] - 1, rank[1] - 1
+                assert {first, second} == {0, 1}
+                assert start[first] == 0 and start[second] == length[first] > 0
+                seen_second += 1
+    assert seen_second >= 2   # 6 or 13 probes of the last key over two windows, per rank
+    for o in range(P):
+        recv, rdir, rmsg = deliver(ins, o)
+        shards[o].shard_insert_chunks(recv, cap, P, rdir, dbytes, tiles, rmsg, 2)
+    torch.cuda.synchronize()
+    ib, io = pkg.keys.pack([x for r in range(P) for x in per_rank[r]])
+    bits = oracle.new_bitset(m, k)
+    oracle.insert_many(bits, m, k, ib, io)
+    assert D.interleave_shards([e.shard_export() for e in shards], shards[0].filter.reach_bits, b) == oracle.redis_string(bits)
+    probes = [per_rank[1 - r][: n // 2] + ["fresh%d-%d" % (r, i) for i in range(n - n // 2)] for r in range(P)]
+    qs = [route(r, probes[r]) for r in range(P)]
+    cap8 = (cap + 7) // 8
+    packed = []
+    for o in range(P):
+        recv, rdir, rmsg = deliver(qs, o)
+        packed.append(shards[o].shard_test_chunks_packed(recv, cap, P, rdir, dbytes, tiles, rmsg, 2))
+    for r in range(P):
+        back = torch.cat([packed[o][r * cap8:(r + 1) * cap8] for o in range(P)])
+        send, slot, counts, dirb, pb, po = qs[r]
+        got = shards[r].combine_chunks_packed(back, slot, cap, dirb, dbytes, tiles, counts, n)
+        np.testing.assert_array_equal(got.cpu().numpy(), oracle.include_many(bits, m, k, pb, po))
+    for e in shards:
+        e.close()
+
+
+@pytest.mark.parametrize("m,k,n", [(95851, 6, 4200), (1000003, 13, 1950)])
+def test_chunk_claims_dropped_run(pkg, oracle, m, k, n):
+    """A window capacity of 12,288 entries under ~12,600 probes per window (P = 2, three or two
+    route tiles): the claim that passes the capacity is dropped.  The claims' order is the
+    hardware's, so the check follows the rank table: the runs' places are the prefix sums of their
+    lengths in rank order, a run that would end past the capacity has the start entry 0xFFFFFFFF
+    and every other run its place, the claim word and the window count end at the window's full
+    total, and every kept run holds exactly its tile's (key, local offset) pairs for that window."""
+    import torch
+    D, P, b = pkg.distributed, 2, 10
+    dev = torch.device("cuda", 0)
+    e = D.HipEngine(m, k, P, 0, b, dev)
+    e.poison = 0xAB   # a dropped run's room keeps the fill: nothing of it may be read as an entry
+    assert e.nh == 1
+    tiles, dbytes = e.chunk_info(n)
+    S = e.filter.route_chunk_info(n)[2]
+    tile_keys = 2048 if k <= 6 else 1024
+    assert tiles == -(-n // tile_keys) >= 2
+    cap = 12288
+    rng = np.random.default_rng(31)
+    keys = ["d-%d" % int(v) for v in rng.integers(0, 10**12, n)]
+    kb, ko, nn, buf, offs = dev_batch(pkg, torch, keys)
+    idx = oracle.indexes_many(buf, offs, m, k).reshape(-1)
+    owner, local = D.block_owner_local(idx, P, b)
+    key_of = np.arange(len(idx)) // k
+    want_c = np.bincount(owner.astype(np.int64), minlength=P)
+    assert (want_c > cap).all()   # both windows overflow
+    for words in (False, True):
+        if words:
+            send, slot, counts, dirb = e.route_chunks(e.hash_keys(kb, ko, nn), None, nn, cap, tiles, dbytes)
+        else:
+            send, slot, counts, dirb = e.route_chunks(kb, ko, nn, cap, tiles, dbytes)
+        torch.cuda.synchronize()
+        assert counts.cpu().numpy().tolist() == want_c.tolist()
+        s_np = send.cpu().numpy().view(np.uint32).astype(np.uint64)
+        sl = slot.cpu().numpy().view(np.uint16).astype(np.int64)
+        for w, (start, length, rank, nclaim, total) in enumerate(_chunk_dirs(dirb, P, dbytes, tiles, S)):
+            assert total == int(want_c[w]) == int(length.sum())
+            assert nclaim == int((length > 0).sum()) == tiles and (rank[nclaim:] == 0).all()
+            order = rank[:nclaim] - 1
+            assert sorted(order.tolist()) == list(range(tiles))
+            place, dropped = 0, 0
+            for t in order:
+                if place + length[t] <= cap:
+                    assert start[t] == place
+                    seg = slice(w * cap + place, w * cap + place + int(length[t]))
+                    mine = (owner == w) & (key_of // tile_keys == t)
+                    assert sorted(zip((sl[seg] + t * tile_keys).tolist(), s_np[seg].tolist())) == \
+                        sorted(zip(key_of[mine].tolist(), local[mine].tolist()))
+                else:
+                    assert start[t] == 0xFFFFFFFF
+                    dropped += 1
+                place += int(length[t])
+            assert dropped >= 1
+    e.close()
