@@ -15,7 +15,8 @@
 //                       through LDS (bfdev::for_key_tile), SHA-1 and the offsets of ruby.rb:41-55
 //                       from bf_device.h, the k probes inside the lane's own filter.
 //   bank_seq_*_kernel   insert with the exact sequential per-key flag (first-seen dedup): bf_seq.hip's
-//                       candidates / mark pair, the first-index table keyed by the bank-wide bit.
+//                       candidates / mark pair, the first-index table (bf_seq_table.h) keyed by the
+//                       bank-wide bit.
 //   bank_list_tile      bf_bank_insert_many_changes*: the LIST instantiations of the two insert
 //                       kernels also list every bit their own atomics flipped, as (filter id,
 //                       SETBIT offset) pairs; slots reserved once per workgroup.
@@ -43,6 +44,7 @@
 #include "bfhip.h"
 #include "bf_device.h"
 #include "bf_host.h"
+#include "bf_seq_table.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -52,6 +54,7 @@
 #include <vector>
 
 using namespace bfdev;
+using namespace bfseq;
 
 namespace {
 
@@ -129,6 +132,20 @@ __device__ __forceinline__ void bank_list_tile(const BfGeom& g, const BankList<t
 
 // status[0]: a key's offsets failed bfdev::key_ok; status[1]: a filter id >= n_filters.
 // Both live in the bank's pinned status block, which bf_bank_sync reports.
+
+// Whether lane's pair (id, key) of a tile of cnt keys is taken.  for_key_tile hands a refused key
+// over as the empty key: its offsets tell the two apart again.  Every lane hashes (the staged
+// SHA-1 reduces over the wave); a refused lane drops out after it.
+__device__ __forceinline__ bool bank_pair_ok(const uint64_t* s_off, uint32_t lane, uint32_t cnt, uint32_t id,
+                                             uint64_t n_filters, uint32_t* status) {
+    bool ok = key_ok(s_off[0], s_off[lane], s_off[lane + 1], s_off[cnt], nullptr);
+    if ((uint64_t)id >= n_filters) {
+        status[1] = 1u;
+        ok = false;
+    }
+    return ok;
+}
+
 // LIST (insert only): every bit a lane's own atomic flipped goes to `list` (bank_list_tile).
 template <int OP, bool LIST = false>
 __global__ __launch_bounds__(kBankTile) void bank_keys_kernel(BfGeom g, uint64_t n_filters, uint64_t stride_words,
@@ -149,14 +166,8 @@ __global__ __launch_bounds__(kBankTile) void bank_keys_kernel(BfGeom g, uint64_t
         [&](auto staged, uint32_t lane, const uint32_t* src, uint32_t s, uint32_t L) {
             const uint64_t j = tile0 + lane;
             const uint32_t id = ids[j];
-            // for_key_tile hands a refused key over as the empty key: tell the two apart again.
-            // Every lane hashes (the staged SHA-1 reduces over the wave), a skipped lane drops
-            // out after it: no bit set, answer 0, key_flipped 0.
-            bool ok = key_ok(s_off[0], s_off[lane], s_off[lane + 1], s_off[cnt], nullptr);
-            if ((uint64_t)id >= n_filters) {
-                status[1] = 1u;
-                ok = false;
-            }
+            // a refused pair: no bit set, answer 0, key_flipped 0
+            const bool ok = bank_pair_ok(s_off, lane, cnt, id, n_filters, status);
             uint32_t H[5];
             sha1_any<decltype(staged)::value>(src, s, L, H);
             if (!ok) {
@@ -235,24 +246,14 @@ __global__ __launch_bounds__(kBankTile) void bank_keys_kernel(BfGeom g, uint64_t
 //
 // A bit is named bank-wide: id * stride * 8 + o, which is also its position in the allocation.
 //   1. bank_seq_candidates: hash, test every probe against the pre-batch bits (plain loads, the
-//      bank is not written) and record the min index j under the bit's number for each 0 bit —
-//      DIRECT: one uint32 per bit of the bank, one atomicMin; else an open-addressing table keyed
-//      by bit number + 1 (64-bit atomicCAS claim, then atomicMin), at most half full.  The digest
-//      and the key's mask of 0-probes go to scratch.
+//      bank is not written) and note the index j under the bit's number for each 0 bit, in the
+//      first-index table of bf_seq_table.h (DIRECT: one uint32 per bit of the bank; else the hash
+//      table).  The digest and the key's mask of 0-probes go to scratch.
 //   2. bank_seq_mark: new(j) from the table, then the 0-probes ORed in.
 // Indices are 32-bit and relative to the chunk (bf_seq_chunk_keys); chunks run in stream order.
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {   // SplitMix64 finalizer, as in bf_seq.hip
-    x ^= x >> 30;
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27;
-    x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-
 // cand[j] = the mask of key j's probes whose bit is 0 (probe i: bit i; k <= BF_MAX_K = 64),
-// digests[j] = H0..H3.  A refused key (bank_keys_kernel's rule) has mask 0.  status as there.
+// digests[j] = H0..H3.  A refused pair (bank_pair_ok) has mask 0.  status as in bank_keys_kernel.
 template <bool DIRECT>
 __global__ __launch_bounds__(kBankTile) void bank_seq_candidates_kernel(
     BfGeom g, uint64_t n_filters, uint64_t stride_words, const uint8_t* __restrict__ keys16,
@@ -267,13 +268,7 @@ __global__ __launch_bounds__(kBankTile) void bank_seq_candidates_kernel(
         [&](auto staged, uint32_t lane, const uint32_t* src, uint32_t s, uint32_t L) {
             const uint32_t j = (uint32_t)(tile0 + lane);   // chunk-relative: n <= 2^22
             const uint32_t id = ids[j];
-            // a refused key arrives as the empty key (bank_keys_kernel): every lane hashes, a
-            // skipped one keeps mask 0
-            bool ok = key_ok(s_off[0], s_off[lane], s_off[lane + 1], s_off[cnt], nullptr);
-            if ((uint64_t)id >= n_filters) {
-                status[1] = 1u;
-                ok = false;
-            }
+            const bool ok = bank_pair_ok(s_off, lane, cnt, id, n_filters, status);   // refused: mask 0
             uint32_t H[5];
             sha1_any<decltype(staged)::value>(src, s, L, H);
             digests[j] = make_uint4(H[0], H[1], H[2], H[3]);
@@ -298,21 +293,7 @@ __global__ __launch_bounds__(kBankTile) void bank_seq_candidates_kernel(
                     for (int c = 0; c < kChunk; ++c) {
                         if ((v[c] >> ((uint32_t)(o[c] ^ 7u) & 31u)) & 1u) continue;   // set already, or past k
                         cm |= 1ull << (i0 + c);
-                        const uint64_t bn = bit0 + o[c];
-                        if constexpr (DIRECT) {   // one word per bit of the bank: no claim, no probing
-                            atomicMin(tvals + bn, j);
-                        } else {
-                            const unsigned long long key = bn + 1;   // 0 marks an empty slot
-                            uint64_t slot = mix64(bn) & tmask;
-                            for (;;) {   // the table holds <= half its slots: a free or matching slot exists
-                                const unsigned long long cur = atomicCAS(tkeys + slot, 0ull, key);
-                                if (cur == 0ull || cur == key) {
-                                    atomicMin(tvals + slot, j);
-                                    break;
-                                }
-                                slot = (slot + 1) & tmask;
-                            }
-                        }
+                        seq_note<DIRECT>(tkeys, tvals, tmask, bit0 + o[c], j);
                     }
                 }
             }
@@ -346,16 +327,7 @@ __global__ __launch_bounds__(kBankTile) void bank_seq_mark_kernel(
                 const uint32_t i = (uint32_t)__builtin_ctzll(cm);
                 cm &= cm - 1;
                 const uint64_t o = probe_offset(g, H.x, H.y, H.z, H.w, i);
-                const uint64_t bn = bit0 + o;
-                uint64_t slot = bn;
-                if constexpr (!DIRECT) {
-                    const unsigned long long key = bn + 1;
-                    slot = mix64(bn) & tmask;
-                    // claimed by bank_seq_candidates; an empty slot cannot come first, it only ends the walk
-                    for (unsigned long long cur = tkeys[slot]; cur != key && cur != 0ull; cur = tkeys[slot])
-                        slot = (slot + 1) & tmask;
-                }
-                isnew |= tvals[slot] == (uint32_t)j ? 1u : 0u;
+                isnew |= seq_first<DIRECT>(tkeys, tvals, tmask, bit0 + o) == (uint32_t)j ? 1u : 0u;
                 const uint32_t bit = 1u << ((uint32_t)(o ^ 7u) & 31u);
                 [[maybe_unused]] const uint32_t old =
                     __hip_atomic_fetch_or(fb + (o >> 5), bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -488,10 +460,6 @@ __global__ __launch_bounds__(kBankTile) void bank_across_kernel(BfGeom g, uint64
 
 // ---- per-filter kernels -------------------------------------------------------------------
 
-__device__ __forceinline__ uint32_t popc4(const uint4& v) {
-    return __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
-}
-
 // 1 + the index of the last non-zero byte of a vector (device byte b is bits 8 (b & 3).. of
 // word b >> 2), 0 for a zero vector.
 __device__ __forceinline__ uint32_t last_byte(const uint4& v) {
@@ -500,17 +468,6 @@ __device__ __forceinline__ uint32_t last_byte(const uint4& v) {
     if (v.y) return 8u - ((uint32_t)__builtin_clz(v.y) >> 3);
     if (v.x) return 4u - ((uint32_t)__builtin_clz(v.x) >> 3);
     return 0u;
-}
-
-// The first `nbytes` (0..16) bytes of a vector, the rest zeroed.
-__device__ __forceinline__ uint4 keep_bytes(uint4 v, uint32_t nbytes) {
-    uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i) {
-        const uint32_t nb = nbytes > 4 * i ? (nbytes - 4 * i < 4 ? nbytes - 4 * i : 4u) : 0u;
-        w[i] &= nb == 4 ? 0xFFFFFFFFu : ((1u << (8 * nb)) - 1u);
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
 // Who owns which listed filter: by stride (a kernel argument, so the choice is
@@ -641,7 +598,7 @@ __global__ __launch_bounds__(kBankLanes) void bank_scatter_kernel(uint4* __restr
         for (uint64_t v = o.lane; v < stride_vec; v += o.lanes) {
             const unsigned long long at = v * 16;
             uint4 x = make_uint4(0u, 0u, 0u, 0u);
-            if (at < len) x = keep_bytes(s[v], len - at < 16 ? (uint32_t)(len - at) : 16u);
+            if (at < len) x = mask_bytes(s[v], 0u, len - at < 16 ? (uint32_t)(len - at) : 16u);
             if (OR) {
                 if (x.x | x.y | x.z | x.w) {
                     const uint4 c = p[v];
@@ -674,13 +631,6 @@ constexpr uint32_t kFoldSliceVec = kBankLanes * kFoldUnroll; // vectors of one w
 constexpr uint64_t kFoldMaxBlocks = 1ull << 22;              // the slice grid: groups stride beyond this
 constexpr uint64_t kFoldMaxSlices = 1024;                    // workgroups of one group: 4 a CU
 static_assert(kFoldSliceStride >= kWaveStrideBytes, "the slice grid is a workgroup's");
-
-template <uint32_t OP>
-__device__ __forceinline__ uint4 fold_op(const uint4& a, const uint4& b) {
-    if constexpr (OP == BF_BITOP_AND) return make_uint4(a.x & b.x, a.y & b.y, a.z & b.z, a.w & b.w);
-    else if constexpr (OP == BF_BITOP_OR) return make_uint4(a.x | b.x, a.y | b.y, a.z | b.z, a.w | b.w);
-    else return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w);
-}
 
 // Group g = src[seg[g]] OP src[seg[g] + 1] OP ... (ruby.rb:59's strings, combined bit for bit as
 // BITOP does).  WRITE: the result replaces filter dst_ids[g], a vector stored only where it
@@ -746,7 +696,7 @@ __global__ __launch_bounds__(kBankLanes) void bank_fold_kernel(uint4* bits, uint
 #pragma unroll
                     for (uint32_t u = 0; u < kFoldUnroll; ++u) {
                         const uint64_t v = vb + (uint64_t)u * o.lanes;
-                        if (v < v1) acc[u] = fold_op<OP>(acc[u], p[v]);
+                        if (v < v1) acc[u] = bitop4<OP>(acc[u], p[v]);
                     }
                 }
 #pragma unroll
@@ -1180,41 +1130,13 @@ int run_dev(bf_bank* b, int op, const uint8_t* d_keys, const uint64_t* d_off, co
 
 constexpr uint64_t kSeqDirectMaxBytes = 1ull << 25;   // a bank of 2^28 bits: a direct table of 1 GiB
 
-uint64_t align256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
-
-// The hash table's slots for n keys of k probes (at most half full): bf_seq.hip's seq_slots.
-uint64_t seq_slots(uint64_t n, uint32_t k) {
-    uint64_t s = 1024;
-    while (s < 2 * n * (uint64_t)k) s <<= 1;
-    return s;
-}
-
-// bf_seq.hip's seq_direct with the bank's bits in place of m: one uint32 per bit of the bank when
-// that table is no larger than the hash table (12 B per slot) it replaces and at most 1 GiB.
-// bf_bank_set_seq_form forces a form where it is legal: the hash form always is, the direct form up
-// to 1 GiB.  cn: the keys of the call's largest chunk.
+// The table's form for a call whose largest chunk has cn keys.  bf_bank_set_seq_form forces a
+// form where it is legal: the hash form always is, the direct form up to 1 GiB.  Otherwise the
+// table's own rule, over the bank's bits.
 bool seq_direct(const bf_bank* b, uint64_t cn) {
-    if (b->seq_form == BF_BANK_SEQ_HASH || b->bytes > kSeqDirectMaxBytes) return false;
-    if (b->seq_form == BF_BANK_SEQ_DIRECT) return true;
-    return 4 * (b->bytes * 8) <= 12 * seq_slots(cn, b->k);
-}
-
-struct BankSeqCarve {
-    unsigned long long* tkeys;   // NULL: the direct form
-    uint32_t* tvals;
-    uint4* digests;
-    unsigned long long* cand;
-    uint64_t slots;
-};
-
-uint64_t seq_table_bytes(const bf_bank* b, bool direct, uint64_t cn) {
-    if (direct) return align256(b->bytes * 8 * 4);
-    const uint64_t slots = seq_slots(cn, b->k);
-    return align256(slots * 8) + align256(slots * 4);
-}
-
-uint64_t seq_scratch_bytes(const bf_bank* b, bool direct, uint64_t cn) {
-    return seq_table_bytes(b, direct, cn) + align256(cn * 16) + align256(cn * 8);
+    if (b->seq_form == BF_BANK_SEQ_HASH) return false;
+    if (b->seq_form == BF_BANK_SEQ_DIRECT) return b->bytes <= kSeqDirectMaxBytes;
+    return seq_direct_fits(b->bytes * 8, cn, b->k);
 }
 
 // How a sequential call of n keys runs (bf_bank_seq_plan reports it): the table's form, the keys
@@ -1229,25 +1151,7 @@ struct BankSeqPlan {
 BankSeqPlan seq_plan(const bf_bank* b, uint64_t n, uint64_t batch_keys) {
     const uint64_t by_width = bf_seq_chunk_keys(b->k), chunk = std::min<uint64_t>(n, std::min<uint64_t>(batch_keys, by_width));
     const bool direct = seq_direct(b, std::min<uint64_t>(n, by_width));
-    return {direct, chunk, chunk ? seq_scratch_bytes(b, direct, chunk) : 0};
-}
-
-BankSeqCarve seq_carve(const bf_bank* b, bool direct, uint64_t cn) {
-    BankSeqCarve c{};
-    uint8_t* at = b->d_seq;
-    if (direct) {
-        c.slots = b->bytes * 8;
-        c.tvals = reinterpret_cast<uint32_t*>(at);
-    } else {
-        c.slots = seq_slots(cn, b->k);
-        c.tkeys = reinterpret_cast<unsigned long long*>(at);
-        c.tvals = reinterpret_cast<uint32_t*>(at + align256(c.slots * 8));
-    }
-    at += seq_table_bytes(b, direct, cn);
-    c.digests = reinterpret_cast<uint4*>(at);
-    at += align256(cn * 16);
-    c.cand = reinterpret_cast<unsigned long long*>(at);
-    return c;
+    return {direct, chunk, chunk ? seq_scratch_bytes(direct, b->bytes * 8, chunk, b->k) : 0};
 }
 
 // The scratch is the bank's and grows on demand.  An earlier call may still use the old buffer
@@ -1269,20 +1173,19 @@ int ensure_seq_scratch(bf_bank* b, uint64_t need) {
 // list: the mark kernel also lists the bits it flipped.
 int launch_seq_chunk(bf_bank* b, bool direct, const uint8_t* d_keys, const uint64_t* d_off, const uint32_t* d_ids,
                      uint64_t cn, uint8_t* d_out8, hipStream_t s, const BankList<true>* list = nullptr) {
-    const BankSeqCarve c = seq_carve(b, direct, cn);
-    if (c.tkeys) HIPCHK(b, hipMemsetAsync(c.tkeys, 0, c.slots * 8, s));
-    HIPCHK(b, hipMemsetAsync(c.tvals, 0xFF, c.slots * 4, s));
+    const SeqCarve c = seq_carve(b->d_seq, direct, b->bytes * 8, cn, b->k);
+    HIPCHK(b, seq_table_clear(c, s));
     uint64_t bias = 0;
     const uint8_t* k16 = align_keys(d_keys, &bias);
     const dim3 grid((uint32_t)((cn + kBankTile - 1) / kBankTile)), block(kBankTile);
-    const uint64_t sw = b->stride / 4, tmask = direct ? 0 : c.slots - 1;
+    const uint64_t sw = b->stride / 4;
 #define BF_SEQ_MARK(DIRECT, LIST, list_arg)                                                                           \
     hipLaunchKernelGGL((bank_seq_mark_kernel<DIRECT, LIST>), grid, block, 0, s, b->g, sw, d_ids, cn, c.tkeys, c.tvals, \
-                       tmask, c.digests, c.cand, d_out8, list_arg)
+                       c.tmask, c.digests, c.cand, d_out8, list_arg)
 #define BF_SEQ_LAUNCH(DIRECT)                                                                                          \
     do {                                                                                                               \
         hipLaunchKernelGGL(bank_seq_candidates_kernel<DIRECT>, grid, block, 0, s, b->g, b->n_filters, sw, k16, d_off,  \
-                           bias, d_ids, cn, c.tkeys, c.tvals, tmask, c.digests, c.cand, b->d_status);                  \
+                           bias, d_ids, cn, c.tkeys, c.tvals, c.tmask, c.digests, c.cand, b->d_status);                \
         if (list) BF_SEQ_MARK(DIRECT, true, *list);                                                                    \
         else BF_SEQ_MARK(DIRECT, false, BankList<false>{});                                                            \
     } while (0)

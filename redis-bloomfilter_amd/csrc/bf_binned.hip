@@ -2227,8 +2227,6 @@ bool apply_pipelined(uint32_t density, uint32_t form, uint32_t region_log2, uint
 // (profiles/r04i_ab_apply_loads.jsonl)
 int region_loads(uint64_t probes, uint32_t nbins) { return probes <= (uint64_t)nbins * 4096u ? 2 : 8; }
 
-uint64_t align256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
-
 struct Carve {
     uint32_t *level1, *level1_key, *level2, *level2_key, *gcnt, *gsum, *base, *cb_base, *cb_window, *cb_start;
     uint16_t *stab, *tabs;

@@ -1,8 +1,10 @@
 // bf_device.h — device-side building blocks shared by the kernels: SHA-1 over
 // LDS-staged packed keys, the ruby driver's offset derivation, the ownership
-// map of partitioned filters, and the workgroup key-tile stager.
+// map of partitioned filters, the workgroup key-tile stager, and the 16-byte
+// vector helpers of the bitset streams.
 #pragma once
 #include "bf_internal.h"
+#include "bfhip.h"   // BF_BITOP_*
 
 #include <type_traits>
 
@@ -296,6 +298,37 @@ __device__ __forceinline__ void report_any_new(uint32_t* any_flag, bool mine) {
     if (b == 0ull || (threadIdx.x & 63u) != (uint32_t)__builtin_ctzll(b)) return;
     if (__hip_atomic_load(any_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;
     __hip_atomic_fetch_or(any_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- 16-byte vectors of a bitset (bf_stats.hip, bf_bank.hip) ----
+
+__device__ __forceinline__ uint32_t popc4(const uint4& v) {
+    return __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
+}
+
+// a OP b, OP one of BF_BITOP_AND / _OR / _XOR (bfhip.h).
+template <uint32_t OP>
+__device__ __forceinline__ uint4 bitop4(const uint4& a, const uint4& b) {
+    static_assert(OP == BF_BITOP_AND || OP == BF_BITOP_OR || OP == BF_BITOP_XOR, "a BF_BITOP_* value");
+    if constexpr (OP == BF_BITOP_AND) return make_uint4(a.x & b.x, a.y & b.y, a.z & b.z, a.w & b.w);
+    else if constexpr (OP == BF_BITOP_OR) return make_uint4(a.x | b.x, a.y | b.y, a.z | b.z, a.w | b.w);
+    else return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w);
+}
+
+// The bytes [lo, hi) of a 16-byte vector (0 <= lo <= hi <= 16), the rest zeroed; device byte b is
+// bits 8 (b & 3) .. of word b >> 2.
+__device__ __forceinline__ uint4 mask_bytes(uint4 v, uint32_t lo, uint32_t hi) {
+    uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) {
+        // the word's bytes below hi, less its bytes below lo (0..4 of the word's four each)
+        const uint32_t bl = lo > 4 * i ? (lo - 4 * i < 4 ? lo - 4 * i : 4u) : 0u;
+        const uint32_t bh = hi > 4 * i ? (hi - 4 * i < 4 ? hi - 4 * i : 4u) : 0u;
+        const uint32_t below_lo = bl == 4 ? 0xFFFFFFFFu : ((1u << (8 * bl)) - 1u);
+        const uint32_t below_hi = bh == 4 ? 0xFFFFFFFFu : ((1u << (8 * bh)) - 1u);
+        w[i] &= below_hi & ~below_lo;
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
 }  // namespace bfdev

@@ -63,7 +63,10 @@ inline uint32_t bf_mod_sub(uint64_t m, uint64_t vmax) {
     return q <= 3 ? (uint32_t)q : 0u;
 }
 
-constexpr uint32_t kDirtyShiftBits = 19;   // dirty-tracking block: 2^19 bits = BF_DIRTY_BLOCK_BYTES of the string
+// Device scratch is carved into parts that each start on a 256-byte boundary.
+inline uint64_t align256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
+
+constexpr uint32_t kDirtyShiftBits = 19;  // dirty-tracking block: 2^19 bits = BF_DIRTY_BLOCK_BYTES of the string
 
 // The sync-free exchange's receive layout: nwin windows of cap entries, window w's live count
 // counts[w * stride] on the device, or none when that exceeds cap (an overflowed window holds

@@ -9,12 +9,10 @@
 //
 // (first(b) <= j always holds for j's own probes).  Two kernels per chunk:
 //   1. seq_candidates: hash (shared SHA-1 / ruby.rb:41-55 derivation), test every
-//      probe against the pre-batch bitset; for each 0 bit record the min index j —
-//      DIRECT: in a table of one uint32 per bit of the filter (one atomicMin at the
-//      offset), for filters whose table is not much larger than the hash table below
-//      (seq_direct: the Lua layout's 1M-scale layers, 44 MB at 11M bits); else in a
-//      global open-addressing table keyed by bit offset (atomicCAS claim + atomicMin);
-//      keep the digest and the key's mask of 0-probes;
+//      probe against the pre-batch bitset; for each 0 bit note the index j in the
+//      first-index table (bf_seq_table.h, shared with the bank: one uint32 per bit of the
+//      filter where that is no bigger than the hash table, else the hash table), keyed by
+//      the bit's offset; keep the digest and the key's mask of 0-probes;
 //   2. seq_mark: new(j) from the table, then OR the 0-probes of keys j < limit in.
 // Filters of up to 2^27 bits and batches of 4096+ keys take the binned form below instead
 // (the table per region of the filter, in LDS; launched behind the same two entry points).
@@ -24,23 +22,16 @@
 // against — is !new(j).  The probe indices are i0 .. i0+k-1: 0-based for the
 // ruby driver (ruby.rb:50), 1-based for the Lua scripts (add.lua:37).
 #include "bf_device.h"
+#include "bf_seq_table.h"
 #include "bfhip.h"   // bf_seq_plan
 
 using namespace bfdev;
+using namespace bfseq;
 
 namespace {
 
 constexpr int kSeqTile = 256;
 constexpr int kSeqStageVec = 16384 / 16;
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {   // SplitMix64 finalizer
-    x ^= x >> 30;
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27;
-    x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
 
 template <bool DIRECT>
 __global__ __launch_bounds__(kSeqTile) void seq_candidates_kernel(BfGeom g, uint32_t i0,
@@ -65,20 +56,7 @@ __global__ __launch_bounds__(kSeqTile) void seq_candidates_kernel(BfGeom g, uint
                 const uint64_t o = probe_offset(g, H[0], H[1], H[2], H[3], i0 + i);
                 if ((g.bits[o >> 5] >> ((uint32_t)(o ^ 7u) & 31u)) & 1u) continue;
                 cm |= 1ull << i;
-                if constexpr (DIRECT) {   // one word per bit (o < m): no claim, no probing
-                    atomicMin(tvals + o, j);
-                    continue;
-                }
-                const unsigned long long key = o + 1;   // 0 marks an empty slot
-                uint64_t slot = mix64(o) & tmask;
-                for (;;) {   // the table holds <= half its slots: a free or matching slot exists
-                    const unsigned long long cur = atomicCAS(tkeys + slot, 0ull, key);
-                    if (cur == 0ull || cur == key) {
-                        atomicMin(tvals + slot, j);
-                        break;
-                    }
-                    slot = (slot + 1) & tmask;
-                }
+                seq_note<DIRECT>(tkeys, tvals, tmask, o, j);
             }
             cand[j] = cm;
         });
@@ -104,13 +82,7 @@ __global__ __launch_bounds__(256) void seq_mark_kernel(BfGeom g, uint32_t i0, ui
                 const uint32_t i = (uint32_t)__builtin_ctzll(cm);
                 cm &= cm - 1;
                 const uint64_t o = probe_offset(g, H.x, H.y, H.z, H.w, i0 + i);
-                uint64_t slot = o;
-                if constexpr (!DIRECT) {
-                    const unsigned long long key = o + 1;
-                    slot = mix64(o) & tmask;
-                    while (tkeys[slot] != key) slot = (slot + 1) & tmask;   // inserted by seq_candidates
-                }
-                isnew |= tvals[slot] == (uint32_t)j ? 1u : 0u;
+                isnew |= seq_first<DIRECT>(tkeys, tvals, tmask, o) == (uint32_t)j ? 1u : 0u;
                 if (j < limit) {
                     const uint32_t bit = 1u << ((uint32_t)(o ^ 7u) & 31u);
                     if (g.dirty) g.dirty[o >> kDirtyShiftBits] = 1;
@@ -309,8 +281,6 @@ __global__ __launch_bounds__(kSeqRegionLanes) void seq_region_kernel(BfGeom g, u
     if (t < nw) g.bits[w0 + t] = s_img[t];
 }
 
-uint64_t align256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
-
 struct SeqBinCarve {
     uint32_t *counts, *base, *cursor;
     uint4* digests;
@@ -341,51 +311,6 @@ uint64_t seq_bin_scratch_bytes(uint64_t n, uint32_t k, uint64_t m) {
     return 3 * align256(seq_regions(m) * 4ull) + align256(n * 16) + align256(n * 8) + align256(n * k * 8);
 }
 
-struct SeqCarve {
-    unsigned long long* tkeys;
-    uint32_t* tvals;
-    uint4* digests;
-    unsigned long long* cand;
-    uint64_t slots;
-};
-
-// The hash table's slots for n keys of k probes (at most half full).
-uint64_t seq_slots(uint64_t n, uint32_t k) {
-    uint64_t s = 1024;
-    while (s < 2 * n * (uint64_t)k) s <<= 1;
-    return s;
-}
-
-// One uint32 per filter bit when that table is no bigger than the hash table (12 B per slot),
-// so neither its clear nor the scratch grows, and at most 1 GiB: the Lua layout's 1M-scale
-// layers (11M bits = 44 MB against a 16M-slot, 192 MB table for a 2^20-key chunk), small
-// filters under big batches.  Probe updates are then one atomicMin each, with no claim loop.
-// (the old bound let the direct table reach twice the hash table's bytes.)
-bool seq_direct(uint64_t n, uint32_t k, uint64_t m) {
-    return m <= (1ull << 28) && 4 * m <= 12 * seq_slots(n, k);
-}
-
-SeqCarve seq_carve(void* scratch, uint64_t n, uint32_t k, uint64_t m) {
-    SeqCarve c{};
-    uint8_t* at = static_cast<uint8_t*>(scratch);
-    if (seq_direct(n, k, m)) {
-        c.slots = m;
-        c.tkeys = nullptr;
-        c.tvals = reinterpret_cast<uint32_t*>(at);
-        at += align256(m * 4);
-    } else {
-        c.slots = seq_slots(n, k);
-        c.tkeys = reinterpret_cast<unsigned long long*>(at);
-        at += align256(c.slots * 8);
-        c.tvals = reinterpret_cast<uint32_t*>(at);
-        at += align256(c.slots * 4);
-    }
-    c.digests = reinterpret_cast<uint4*>(at);
-    at += align256(n * 16);
-    c.cand = reinterpret_cast<unsigned long long*>(at);
-    return c;
-}
-
 }  // namespace
 
 uint64_t bf_seq_chunk_keys(uint32_t k) {
@@ -395,17 +320,16 @@ uint64_t bf_seq_chunk_keys(uint32_t k) {
 
 uint64_t bf_seq_scratch_bytes(uint64_t n, uint32_t k, uint64_t m) {
     if (seq_binned(n, m)) return seq_bin_scratch_bytes(n, k, m);
-    const uint64_t tab = seq_direct(n, k, m) ? align256(m * 4) : align256(seq_slots(n, k) * 8) + align256(seq_slots(n, k) * 4);
-    return tab + align256(n * 16) + align256(n * 8);
+    return seq_scratch_bytes(seq_direct_fits(m, n, k), m, n, k);
 }
 
 // Which form the two launchers below take for a chunk of n keys: the predicates they branch on.
 extern "C" int bf_seq_plan(uint64_t n, uint32_t k, uint64_t m, uint32_t* form, uint64_t* slots,
                            uint64_t* scratch_bytes) {
     if (k == 0 || k > BF_MAX_K || m == 0) return BF_EINVAL;
-    const bool binned = seq_binned(n, m), direct = !binned && seq_direct(n, k, m);
+    const bool binned = seq_binned(n, m), direct = !binned && seq_direct_fits(m, n, k);
     if (form) *form = binned ? BF_SEQ_BINNED : direct ? BF_SEQ_DIRECT : BF_SEQ_HASH;
-    if (slots) *slots = binned ? seq_regions(m) : direct ? m : seq_slots(n, k);
+    if (slots) *slots = binned ? seq_regions(m) : seq_table_slots(direct, m, n, k);
     if (scratch_bytes) *scratch_bytes = bf_seq_scratch_bytes(n, k, m);
     return BF_OK;
 }
@@ -432,16 +356,16 @@ hipError_t bf_launch_seq_candidates(const BfGeom& g, uint32_t i0, const uint8_t*
                            c.cand, c.cursor, c.entries);
         return hipGetLastError();
     }
-    const SeqCarve c = seq_carve(scratch, n, g.k, g.m);
-    if (c.tkeys && (e = hipMemsetAsync(c.tkeys, 0, c.slots * 8, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(c.tvals, 0xFF, c.slots * 4, s)) != hipSuccess) return e;
+    const bool direct = seq_direct_fits(g.m, n, g.k);
+    const SeqCarve c = seq_carve(scratch, direct, g.m, n, g.k);
+    if ((e = seq_table_clear(c, s)) != hipSuccess) return e;
     const uint32_t blocks = (uint32_t)((n + kSeqTile - 1) / kSeqTile);
-    if (c.tkeys)
-        hipLaunchKernelGGL(seq_candidates_kernel<false>, dim3(blocks), dim3(kSeqTile), 0, s, g, i0, keys16, offsets,
-                           bias, n, c.tkeys, c.tvals, c.slots - 1, c.digests, c.cand);
-    else
+    if (direct)
         hipLaunchKernelGGL(seq_candidates_kernel<true>, dim3(blocks), dim3(kSeqTile), 0, s, g, i0, keys16, offsets,
-                           bias, n, c.tkeys, c.tvals, 0, c.digests, c.cand);
+                           bias, n, c.tkeys, c.tvals, c.tmask, c.digests, c.cand);
+    else
+        hipLaunchKernelGGL(seq_candidates_kernel<false>, dim3(blocks), dim3(kSeqTile), 0, s, g, i0, keys16, offsets,
+                           bias, n, c.tkeys, c.tvals, c.tmask, c.digests, c.cand);
     return hipGetLastError();
 }
 
@@ -456,13 +380,14 @@ hipError_t bf_launch_seq_mark(const BfGeom& g, uint32_t i0, uint64_t n, uint64_t
                            c.counts, c.entries, out8, any_flag);
         return hipGetLastError();
     }
-    const SeqCarve c = seq_carve(scratch, n, g.k, g.m);
-    if (c.tkeys)
-        hipLaunchKernelGGL(seq_mark_kernel<false>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, g, i0, n, limit,
-                           d_limit, c.tkeys, c.tvals, c.slots - 1, c.digests, c.cand, out8, any_flag);
-    else
+    const bool direct = seq_direct_fits(g.m, n, g.k);
+    const SeqCarve c = seq_carve(scratch, direct, g.m, n, g.k);
+    if (direct)
         hipLaunchKernelGGL(seq_mark_kernel<true>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, g, i0, n, limit,
-                           d_limit, c.tkeys, c.tvals, 0, c.digests, c.cand, out8, any_flag);
+                           d_limit, c.tkeys, c.tvals, c.tmask, c.digests, c.cand, out8, any_flag);
+    else
+        hipLaunchKernelGGL(seq_mark_kernel<false>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, g, i0, n, limit,
+                           d_limit, c.tkeys, c.tvals, c.tmask, c.digests, c.cand, out8, any_flag);
     return hipGetLastError();
 }
 

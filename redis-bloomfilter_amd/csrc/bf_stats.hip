@@ -6,7 +6,9 @@
 // All three kernels are pure streams: uint4 loads, 256-lane workgroups, at most kMaxBlocks
 // workgroups that stride over the rest, per-lane 64-bit counts reduced per wave (shuffles) and
 // per workgroup (LDS), then ONE 64-bit atomicAdd per workgroup.
-#include "bf_internal.h"
+#include "bf_device.h"
+
+using namespace bfdev;
 
 namespace {
 
@@ -15,19 +17,6 @@ constexpr uint32_t kMaxBlocks = 2048;                       // 8 workgroups per 
 constexpr uint32_t kBlockVecs = (1u << kDirtyShiftBits) / 128;   // uint4 per dirty-tracking block: 4096
 constexpr uint32_t kVecsPerLane = kBlockVecs / kLanes;      // 16
 static_assert(kVecsPerLane * kLanes == kBlockVecs, "a dirty block is a whole number of workgroup passes");
-
-enum : uint32_t { OP_AND = 0, OP_OR = 1, OP_XOR = 2 };
-
-__device__ __forceinline__ uint32_t popc4(const uint4& v) {
-    return __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
-}
-
-template <uint32_t OP>
-__device__ __forceinline__ uint4 combine(const uint4& a, const uint4& b) {
-    if (OP == OP_AND) return make_uint4(a.x & b.x, a.y & b.y, a.z & b.z, a.w & b.w);
-    if (OP == OP_OR) return make_uint4(a.x | b.x, a.y | b.y, a.z | b.z, a.w | b.w);
-    return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w);
-}
 
 // Sum of `acc` over the workgroup, added to *d_count by one lane.
 __device__ __forceinline__ void block_add(unsigned long long acc, unsigned long long* d_count) {
@@ -42,24 +31,6 @@ __device__ __forceinline__ void block_add(unsigned long long acc, unsigned long 
         for (uint32_t w = 0; w < kLanes / 64; ++w) t += s_part[w];
         if (t) atomicAdd(d_count, t);
     }
-}
-
-// The bytes [lo, hi) of a 16-byte vector (0 <= lo < hi <= 16); device byte b is bits
-// 8 (b & 3) .. of word b >> 2.
-__device__ __forceinline__ uint4 mask_bytes(uint4 v, uint32_t lo, uint32_t hi) {
-    uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i) {
-        const uint32_t bl = lo > 4 * i ? (lo - 4 * i < 4 ? lo - 4 * i : 4u) : 0u;
-        const uint32_t bh = hi > 4 * i ? (hi - 4 * i < 4 ? hi - 4 * i : 4u) : 0u;
-        uint32_t mk = 0;
-        if (bh > bl) {
-            mk = bh == 4 ? 0xFFFFFFFFu : ((1u << (8 * bh)) - 1u);
-            mk &= ~((1u << (8 * bl)) - 1u);   // bl < 4 here
-        }
-        w[i] &= mk;
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
 // Set bits of bytes [byte_start, byte_start + byte_len), byte_len > 0, inside the bitset.
@@ -100,10 +71,10 @@ __global__ __launch_bounds__(kLanes) void bitcount_op_kernel(const uint4* __rest
     for (; i + 3 * stride < nvec; i += 4 * stride) {
         const uint4 a0 = a[i], a1 = a[i + stride], a2 = a[i + 2 * stride], a3 = a[i + 3 * stride];
         const uint4 b0 = b[i], b1 = b[i + stride], b2 = b[i + 2 * stride], b3 = b[i + 3 * stride];
-        acc += popc4(combine<OP>(a0, b0)) + popc4(combine<OP>(a1, b1)) + popc4(combine<OP>(a2, b2)) +
-               popc4(combine<OP>(a3, b3));
+        acc += popc4(bitop4<OP>(a0, b0)) + popc4(bitop4<OP>(a1, b1)) + popc4(bitop4<OP>(a2, b2)) +
+               popc4(bitop4<OP>(a3, b3));
     }
-    for (; i < nvec; i += stride) acc += popc4(combine<OP>(a[i], b[i]));
+    for (; i < nvec; i += stride) acc += popc4(bitop4<OP>(a[i], b[i]));
     block_add(acc, d_count);
 }
 
@@ -137,7 +108,7 @@ __global__ __launch_bounds__(kLanes) void bitop_kernel(uint4* __restrict__ dst, 
             for (uint32_t u = 0; u < 8; ++u) {
                 const uint64_t i = base + (uint64_t)(h + u) * kLanes;
                 if (i < nvec) {
-                    const uint4 r = combine<OP>(a[u], b[u]);
+                    const uint4 r = bitop4<OP>(a[u], b[u]);
                     acc += popc4(r);
                     if ((r.x ^ a[u].x) | (r.y ^ a[u].y) | (r.z ^ a[u].z) | (r.w ^ a[u].w)) {
                         dst[i] = r;
@@ -176,9 +147,9 @@ hipError_t bf_launch_bitcount_op(uint32_t op, const uint32_t* a, const uint32_t*
     const uint4* va = reinterpret_cast<const uint4*>(a);
     const uint4* vb = reinterpret_cast<const uint4*>(b);
     const dim3 grid(stream_blocks(nvec)), block(kLanes);
-    if (op == OP_AND) hipLaunchKernelGGL(bitcount_op_kernel<OP_AND>, grid, block, 0, s, va, vb, nvec, d_count);
-    else if (op == OP_OR) hipLaunchKernelGGL(bitcount_op_kernel<OP_OR>, grid, block, 0, s, va, vb, nvec, d_count);
-    else if (op == OP_XOR) hipLaunchKernelGGL(bitcount_op_kernel<OP_XOR>, grid, block, 0, s, va, vb, nvec, d_count);
+    if (op == BF_BITOP_AND) hipLaunchKernelGGL(bitcount_op_kernel<BF_BITOP_AND>, grid, block, 0, s, va, vb, nvec, d_count);
+    else if (op == BF_BITOP_OR) hipLaunchKernelGGL(bitcount_op_kernel<BF_BITOP_OR>, grid, block, 0, s, va, vb, nvec, d_count);
+    else if (op == BF_BITOP_XOR) hipLaunchKernelGGL(bitcount_op_kernel<BF_BITOP_XOR>, grid, block, 0, s, va, vb, nvec, d_count);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -191,8 +162,8 @@ hipError_t bf_launch_bitop(uint32_t op, uint32_t* dst, const uint32_t* src, uint
     const dim3 grid(nblk > kMaxBlocks ? kMaxBlocks : (uint32_t)nblk), block(kLanes);
     uint4* vd = reinterpret_cast<uint4*>(dst);
     const uint4* vs = reinterpret_cast<const uint4*>(src);
-    if (op == OP_AND) hipLaunchKernelGGL(bitop_kernel<OP_AND>, grid, block, 0, s, vd, vs, nvec, dirty, d_changed, d_count);
-    else if (op == OP_OR) hipLaunchKernelGGL(bitop_kernel<OP_OR>, grid, block, 0, s, vd, vs, nvec, dirty, d_changed, d_count);
+    if (op == BF_BITOP_AND) hipLaunchKernelGGL(bitop_kernel<BF_BITOP_AND>, grid, block, 0, s, vd, vs, nvec, dirty, d_changed, d_count);
+    else if (op == BF_BITOP_OR) hipLaunchKernelGGL(bitop_kernel<BF_BITOP_OR>, grid, block, 0, s, vd, vs, nvec, dirty, d_changed, d_count);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

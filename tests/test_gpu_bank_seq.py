@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from test_gpu_bank import M, K, Model, check_bank, dev_batch, make_keys, pack
+from test_gpu_seq_hash_and_cut import half_batch, wraps
 
 pytestmark = pytest.mark.gpu
 
@@ -331,6 +332,117 @@ def test_dev_form_cuts_a_long_batch_itself(pkg, oracle, monkeypatch):
         assert np.array_equal(got, want)
         assert got[[cut - 1, cut, 5, cut + 200]].tolist() == [1, 0, 1, 0]
         assert bank.export_redis() == strings
+
+
+# ---- the first-index table: one rule with the single filter's, and the hash table's edges --------
+
+@pytest.mark.parametrize("n_filters,line", [(2, 342), (5, 1366)])
+def test_bank_plan_follows_the_filter_rule(pkg, monkeypatch, n_filters, line):
+    """A bank of B bits takes the direct form exactly when a single filter of m = B bits does (one
+    word per bit is no bigger than the hash table: 4 B <= 12 slots), with the same scratch.
+    ``line`` is the first n on the direct side; all n are below 4096, where the single filter's
+    plan turns to the binned form."""
+    def slots(n):                                                     # the hash table: >= 2 n k, at least 1024
+        return max(1024, 1 << (2 * n * K - 1).bit_length())
+
+    with make_bank(pkg, monkeypatch, None, M, K, n_filters) as bank:
+        B = bank.device_bytes * 8                                     # bf_bank_info
+        assert B == n_filters * 10240
+        assert 4 * B > 12 * slots(line - 1) and 4 * B <= 12 * slots(line)
+        for n in (1, 85, 86, line - 1, line, line + 1, 2730, 2731, 4095):
+            single = pkg._lib.seq_plan(n, K, B)
+            assert single["form"] == (1 if n >= line else 0)          # BF_SEQ_DIRECT / BF_SEQ_HASH
+            assert single["slots"] == (B if n >= line else slots(n))
+            direct, chunk, scratch = bank.seq_plan(n)
+            assert direct is (n >= line) and chunk == n
+            assert scratch == single["scratch_bytes"]
+
+
+TABLE_POINTS = ["seq", "dev", "changes"]     # bf_bank_insert_many_seq, _seq_dev, _changes with seq = 1
+
+
+def align256(x):
+    return (x + 255) & ~255
+
+
+def bank_bits(pkg, oracle, bank, keys, ids):
+    """Every probe of the batch by its bank-wide bit number, the first-index table's key."""
+    idx = oracle.indexes_many(*pkg.keys.pack(keys), bank.m, bank.k)
+    return [int(f) * bank.stride * 8 + int(o) for f, row in zip(ids, idx) for o in row]
+
+
+def table_case(pkg, oracle, monkeypatch, point, m, k, n_filters, batches, precondition):
+    """Batches of a 1024-slot hash table through one entry point of a fresh bank, each exact against
+    the oracle's one-by-one loop (flags, strings; the changes call also its list).  Returns the
+    flags of every batch."""
+    from test_gpu_bank_changes import changes_and_check              # it imports this module
+    model = SeqModel(oracle, m, k)
+    out = []
+    with make_bank(pkg, monkeypatch, "hash", m, k, n_filters) as bank:
+        assert not bank.bitcount().any()
+        precondition(bank_bits(pkg, oracle, bank, *batches[0]))
+        for keys, ids in batches:
+            n = len(keys)
+            assert 2 * n * k <= 1024
+            assert bank.seq_plan(n) == (False, n, 1024 * 12 + align256(n * 16) + align256(n * 8))
+            if point == "seq":
+                flags = seq_and_check(bank, model, keys, ids, n_filters)
+            elif point == "changes":
+                flags, _ = changes_and_check(bank, model, keys, ids, n_filters, True)
+            else:
+                dk, do, di = dev_batch(keys, ids)
+                d_flags = torch.full((n,), 7, dtype=torch.uint8, device="cuda")
+                torch.cuda.synchronize()
+                bank.insert_many_seq_dev(dk.data_ptr(), do.data_ptr(), di.data_ptr(), n, d_flags.data_ptr())
+                bank.sync()
+                flags = d_flags.cpu().numpy()
+                assert np.array_equal(flags, model.insert_seq(keys, ids))
+                check_bank(bank, model, n_filters)
+            out.append(flags.astype(bool))
+    return out
+
+
+# Found by a search over seeds on the CPU (about one seed in fifteen wraps); the test asserts its
+# seed's property before it runs, so a changed key format or hash cannot lapse unnoticed.
+BANK_WRAP_SEED, BANK_HALF_SEED = 1, 2
+
+
+@pytest.mark.parametrize("point", TABLE_POINTS)
+def test_bank_hash_table_wraps(pkg, oracle, monkeypatch, point):
+    """73 pairs over 5 filters (2 n k = 876: 1024 slots): two distinct bank-wide bits of the batch
+    hash to slot 1023, so one of them is stored at slot 0 and the mark's lookup follows it there.
+    60 keys are distinct, 13 come again: 7 to the same filter (not new), 6 wherever the ids fall."""
+    keys = [b"bw%d-%d" % (BANK_WRAP_SEED, i) for i in range(60)]
+    keys = keys[:30] + keys[:13] + keys[30:]
+    ids = np.random.default_rng(BANK_WRAP_SEED).integers(0, 5, len(keys)).astype(np.uint32)
+    ids[30:37] = ids[:7]
+    again = keys[::2] + [b"x" + key for key in keys[1::2]]           # half of the keys replaced
+    again_ids = np.concatenate([ids[::2], ids[1::2]])
+
+    def two_bits_at_the_last_slot(bits):
+        assert wraps(bits, 1024)
+
+    flags = table_case(pkg, oracle, monkeypatch, point, M, K, 5, [(keys, ids), (again, again_ids)],
+                       two_bits_at_the_last_slot)
+    assert not flags[0][30:37].any() and flags[0][:30].all() and flags[0][43:].all()
+    assert not flags[1][:37].any() and 0 < flags[1][37:].sum() < 36  # a replaced key that comes twice is new once
+
+
+@pytest.mark.parametrize("point", TABLE_POINTS)
+def test_bank_hash_table_half_full(pkg, oracle, monkeypatch, point):
+    """64 keys of 8 probes over 2 filters of 2^20 bits, all 512 bank-wide bits distinct and 0:
+    2 n k = 1024 slots, exactly half of them taken.  The batch again (no 0-probe at all), then
+    half of it with new keys."""
+    m, k = 1 << 20, 8
+    keys = half_batch(BANK_HALF_SEED)
+    ids = (np.arange(64) % 2).astype(np.uint32)
+
+    def all_distinct(bits):                                           # and 0: the bank is empty
+        assert len(bits) == 512 == len(set(bits))
+
+    mixed = keys[:32] + half_batch(BANK_HALF_SEED + 1)[:32]
+    flags = table_case(pkg, oracle, monkeypatch, point, m, k, 2, [(keys, ids), (keys, ids), (mixed, ids)], all_distinct)
+    assert flags[0].all() and not flags[1].any() and not flags[2][:32].any() and flags[2][32:].all()
 
 
 # ---- the host form's refusals ---------------------------------------------------------------------

@@ -297,7 +297,7 @@ M64 = (1 << 64) - 1
 
 
 def mix64(x):
-    """bf_seq.hip's slot hash: the SplitMix64 finalizer."""
+    """bf_seq_table.h's slot hash: the SplitMix64 finalizer."""
     x ^= x >> 30
     x = x * 0xBF58476D1CE4E5B9 & M64
     x ^= x >> 27
@@ -450,6 +450,22 @@ def test_hash_table_half_full_lua(pkg, point):
     assert len({o for row in lua_probes(keys, m, k) for o in row}) == 512
     flags = lua_case(pkg, point, HALF_LUA, [keys, keys, keys[:32] + half_batch(HALF_SEED_LUA + 1)[:32]], 1024)
     assert flags[0].all() and not flags[1].any() and not flags[2][:32].any() and flags[2][32:].all()
+
+
+@pytest.mark.parametrize("point", ["host", "dev"])
+def test_hash_table_lookup_walks_filter(pkg, oracle, point):
+    """k = 1: a key's flag rests on its one probe, so a lookup that stops short of a displaced bit
+    shows in the flag (with more probes another new bit of the key hides it).  512 keys, 448
+    distinct and 64 of them again: 2 n k = 1024 slots; at least ten bits share their home slot
+    with another and are stored further on."""
+    m, k = 95851, 1
+    keys = [b"d%d" % i for i in range(448)]
+    keys = keys[:200] + keys[:64] + keys[200:]
+    offsets = set(oracle.indexes_many(*pkg.keys.pack(keys), m, k).reshape(-1).tolist())
+    homes = [mix64(o) & 1023 for o in offsets]
+    assert len(homes) - len(set(homes)) >= 10
+    flags = filter_case(pkg, oracle, point, m, k, [keys], 1024)
+    assert not flags[0][200:264].any() and flags[0].sum() == len(offsets)
 
 
 @pytest.mark.parametrize("point", ["host", "dev"])
