@@ -269,8 +269,8 @@ int  bf_insert_plan(const bf_handle* h, uint64_t n, uint32_t* binned, uint64_t* 
  * picks its kernels from the shape of the call; every field below comes from the predicate
  * the launch code itself branches on, so a test can assert the variant it is about.  A batch
  * larger than one binned launch takes goes in `passes` sub-batches; everything else describes
- * the first of them.  Libraries built with the A/B knobs (-DBFHIP_AB_KNOBS) describe the
- * defaults: a knob's override of a variant is not reflected here. */
+ * the first of them.  An A/B build (-DBFHIP_AB_KNOBS) whose open experiment overrides a
+ * variant still describes the defaults here. */
 typedef struct bf_plan_detail {
     uint64_t passes;          /* sub-batches (launches) the batch is cut into */
     uint64_t tiles;           /* front tiles of the sub-batch */

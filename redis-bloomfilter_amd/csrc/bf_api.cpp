@@ -144,7 +144,6 @@ struct bf_handle : BfHostCore {
     uint32_t k = 0;
     // partitioned filters: this handle holds shard `shard_index` of `shards`
     uint32_t shards = 1, shard_index = 0, block_log2 = 20;
-    uint32_t mem_kind = 0;   // bitset allocation: 0 coarse-grained, 1 uncached, 2 fine-grained
     bool route32 = false;    // BF_FLAG_ROUTE32
     uint32_t engine = BF_ENGINE_RUBY;   // BF_FLAG_ENGINE_*: the RubyTest hash engines
     uint64_t local_bits = 0;
@@ -163,8 +162,7 @@ struct bf_handle : BfHostCore {
     // the north-star shards at P = 2..8): 0.89 ms against 1.08 for sort + region test, 3.22 vs
     // 3.38 ms per P = 8 rank step.  Otherwise (8 MiB+ superbins, e.g. 200B x 8: 3.44 vs 3.11 ms)
     // it sorts, with 256 buckets (longer runs for the owner's mid).  profiles/r03_sim_chunks_P8.jsonl.
-    // BFHIP_CHUNK_BUCKETS forces the bucket count, BFHIP_CHUNK_TEST_L2=0/1 the test (A/B only).
-    uint32_t chunk_buckets = 0;   // 0: auto
+    // BFHIP_CHUNK_TEST_L2=0/1 forces the test.
     uint32_t chunk_test_l2 = 2;   // 2: auto
     void* d_bin_scratch = nullptr;   // digests, probe arrays and histograms of one binned launch
     uint64_t bin_scratch_cap = 0;
@@ -235,11 +233,9 @@ int handle_open(CallScope& cs, bf_handle* h, hipStream_t s, bool needs_bits = tr
 
 uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
-// Probe-policy defaults, measured on MI355X with tools/ab_policies.py (profiles/
-// ab_policies_r01.jsonl): include? loads ceil(k/4) probes before its first
-// early-exit check (1B@1%: 1.82 -> 1.39 ms per 2^24 keys), insert loads the k
-// words and atomics only the unset bits (5.13 -> 3.30 ms).  The environment
-// overrides exist for A/B runs and never change results.
+// Probe-policy defaults, measured on MI355X (profiles/ab_policies_r01.jsonl): include? loads
+// ceil(k/4) probes before its first early-exit check (1B@1%: 1.82 -> 1.39 ms per 2^24 keys),
+// insert loads the k words and atomics only the unset bits (5.13 -> 3.30 ms).
 // include? probe rounds.  A bitset beyond the caches: one word at a time, stopping at the first
 // 0 bit (ruby.rb:23's early exit at every probe), so a non-member costs ~2 line fills instead of
 // ceil(k/4) + a round of the rest — 1B@1 % (k = 6) 1.45 -> 1.32 ms, 100M@0.1 % (k = 10)
@@ -249,7 +245,6 @@ constexpr uint64_t kSequentialProbeBytes = 64ull << 20;
 uint32_t default_first_round(uint32_t k, uint64_t bytes) { return bytes > kSequentialProbeBytes ? 1 : (k + 3) / 4; }
 uint32_t default_next_round(uint64_t bytes) { return bytes > kSequentialProbeBytes ? 1 : 0; }
 constexpr uint32_t kDefaultInsertTest = 1;
-constexpr uint32_t kDefaultMemKind = 0;
 constexpr uint32_t kDefaultBinnedMode = 2;     // auto
 // include? stays on the direct kernel by default: at 1B@1% (2^24 keys) the binned
 // include? measured 1.92 ms against 1.48 ms direct (hash 0.76 + partition 0.43 +
@@ -861,16 +856,11 @@ int bf_create(uint64_t m_bits, uint32_t k, const bf_config* cfg, bf_handle** out
     hipError_t e;
     if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return fail(BF_EDEVICE, "hipStreamCreate", e);
     if ((e = hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming)) != hipSuccess) return fail(BF_EDEVICE, "hipEventCreate", e);
-    // Bitset memory kind (A/B knob): 0 coarse-grained hipMalloc, 1 uncached (MTYPE UC),
-    // 2 fine-grained.
-    h->mem_kind = ab_u32("BFHIP_BITS_MEM", kDefaultMemKind);
     // BF_FLAG_ENCODER: the filter's geometry without its bitset (a second handle that encodes a
     // replicated filter's next batch beside its apply: bf_encode_region_sets*_dev only)
     const bool encoder = (c.flags & BF_FLAG_ENCODER) != 0;
     if (encoder) e = hipSuccess;
-    else if (h->mem_kind == 1) e = hipExtMallocWithFlags((void**)&h->g.bits, h->dev_bytes, hipDeviceMallocUncached);
-    else if (h->mem_kind == 2) e = hipExtMallocWithFlags((void**)&h->g.bits, h->dev_bytes, hipDeviceMallocFinegrained);
-    else e = hipMalloc((void**)&h->g.bits, h->dev_bytes);
+    else e = hipMalloc((void**)&h->g.bits, h->dev_bytes);   // coarse-grained
     if (e != hipSuccess) return fail(BF_ENOMEM, "hipMalloc(bitset)", e);
     if ((e = hipMalloc((void**)&h->d_flag, 256)) != hipSuccess) return fail(BF_ENOMEM, "hipMalloc(flag)", e);
     if ((e = hipMalloc((void**)&h->d_scan, 256)) != hipSuccess) return fail(BF_ENOMEM, "hipMalloc(scan)", e);
@@ -889,8 +879,7 @@ int bf_create(uint64_t m_bits, uint32_t k, const bf_config* cfg, bf_handle** out
     h->g.nomod = (m_bits > maxval) ? 1u : 0u;
     h->g.mod_f32 = (m_bits >= (1ull << 17)) ? 1u : 0u;
     h->g.inv_m_f = (float)(1.0 / (double)m_bits);
-    // BFHIP_MOD_SUB=0: the float-estimate modulo everywhere (A/B)
-    h->g.mod_sub = ab_u32("BFHIP_MOD_SUB", 1) ? bf_mod_sub(m_bits, (uint64_t)k * 0xFFFFFFFFull) : 0u;
+    h->g.mod_sub = bf_mod_sub(m_bits, (uint64_t)k * 0xFFFFFFFFull);
     h->g.shards = h->shards;
     h->g.block_log2 = h->block_log2;
     h->g.inv_shards = 1.0 / (double)h->shards;
@@ -898,13 +887,12 @@ int bf_create(uint64_t m_bits, uint32_t k, const bf_config* cfg, bf_handle** out
     h->g.shard_log2 = (uint32_t)__builtin_ctz(h->shards);
     h->g.route32 = h->route32 ? 1u : 0u;
     h->g.limit = h->local_bits;
-    h->g.first_round = ab_u32("BFHIP_INCLUDE_FIRST_ROUND", default_first_round(k, h->dev_bytes));
-    h->g.next_round = ab_u32("BFHIP_INCLUDE_NEXT_ROUND", default_next_round(h->dev_bytes));
+    h->g.first_round = default_first_round(k, h->dev_bytes);
+    h->g.next_round = default_next_round(h->dev_bytes);
     h->g.route_agg = env_u32("BFHIP_ROUTE_AGG", 1);   // P = 1 only: at P = 8 the per-owner loop costs more than the LDS atomics (sim_rank A/B)
-    h->g.insert_test = ab_u32("BFHIP_INSERT_TEST", kDefaultInsertTest);
+    h->g.insert_test = kDefaultInsertTest;
     h->binned_mode = env_u32("BFHIP_INSERT_BINNED", kDefaultBinnedMode);
     h->bin_region_log2 = env_u32("BFHIP_BIN_REGION_LOG2", kDefaultBinRegionLog2);
-    h->chunk_buckets = ab_u32("BFHIP_CHUNK_BUCKETS", 0);
     h->chunk_test_l2 = env_u32("BFHIP_CHUNK_TEST_L2", 2);
     h->include_binned_mode = env_u32("BFHIP_INCLUDE_BINNED", kDefaultIncludeBinnedMode);
     h->shard_test_binned_mode = env_u32("BFHIP_SHARD_TEST_BINNED", 2);
@@ -1272,10 +1260,7 @@ static bool handle_chunks(const bf_handle* h, BfChunks* cg, uint32_t* nh_out, bo
     if (nh_out) *nh_out = nh;
     const uint32_t nwin = h->shards * nh;
     bool sweep = false;
-    if (h->chunk_buckets) {   // forced
-        if (!bf_chunk_geometry(bits0, nwin, h->bin_region_log2, cg, h->chunk_buckets)) return false;
-        sweep = h->chunk_test_l2 == 1 || (h->chunk_test_l2 == 2 && cg->sup_log2 <= kL2SweepMaxSupLog2);
-    } else if (h->chunk_test_l2 != 0 && bf_chunk_geometry(bits0, nwin, h->bin_region_log2, cg, 512) &&
+    if (h->chunk_test_l2 != 0 && bf_chunk_geometry(bits0, nwin, h->bin_region_log2, cg, 512) &&
                (h->chunk_test_l2 == 1 || cg->sup_log2 <= kL2SweepMaxSupLog2)) {
         sweep = true;
     } else if (!bf_chunk_geometry(bits0, nwin, h->bin_region_log2, cg, 256)) {

@@ -36,7 +36,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 
 using namespace bfdev;
 
@@ -231,7 +230,7 @@ void bin_front_kernel(BfGeom g, const uint8_t* __restrict__ keys16, const uint64
 }
 
 // 12 < k <= 16: 16 probe slots per lane (64 KiB sort buffer, one workgroup per CU)
-template <bool KEYS, bool DIG = false>
+template <bool KEYS>
 __global__ __launch_bounds__(kTile) void bin_front_wide_kernel(BfGeom g, const uint8_t* __restrict__ keys16,
                                                                const uint64_t* __restrict__ offsets, uint64_t bias,
                                                                uint64_t n, uint32_t tile_keys,
@@ -240,8 +239,8 @@ __global__ __launch_bounds__(kTile) void bin_front_wide_kernel(BfGeom g, const u
                                                                uint32_t* __restrict__ level1_key,
                                                                uint16_t* __restrict__ stab, uint32_t* __restrict__ gcnt,
                                                                uint8_t* __restrict__ out8) {
-    bin_front_body<KEYS, kWideSlots, DIG>(g, keys16, offsets, bias, n, tile_keys, tiles_per_block, sup_log2, nsup,
-                                          level1, level1_key, stab, gcnt, out8);
+    bin_front_body<KEYS, kWideSlots>(g, keys16, offsets, bias, n, tile_keys, tiles_per_block, sup_log2, nsup,
+                                     level1, level1_key, stab, gcnt, out8);
 }
 
 // ... from SHA-1 words (the pipelined insert at k > 12: 10B / 200B): no key stage, so 67 KiB
@@ -1322,7 +1321,7 @@ __global__ __launch_bounds__(LANES) void bin_apply_kernel(uint32_t* __restrict__
                                                           uint32_t xg) {
     constexpr uint32_t kVec = 1u << (RLOG2 - 7);   // 16-B vectors per region
     constexpr uint32_t kPer = kVec / LANES;
-    constexpr int kLoads = LOADS;   // level-2 loads per lane and gather step (BFHIP_APPLY_LOADS)
+    constexpr int kLoads = LOADS;   // level-2 loads per lane and gather step (region_loads)
     static_assert(kPer * LANES == kVec, "region must tile the workgroup");
     __shared__ uint4 s_mask4[kVec];
     __shared__ uint32_t s_pre[kRunsPerPass], s_gst[kRunsPerPass], s_w[16];
@@ -1396,7 +1395,7 @@ __global__ __launch_bounds__(LANES) void bin_apply_kernel(uint32_t* __restrict__
 // run-table buffers alternate between r and r + G, the register buffers by unrolling the
 // region loop twice (a register copy would wait for the stores just issued).
 constexpr int kWaitVm0 = 0x0F70;   // s_waitcnt vmcnt(0) expcnt(7) lgkmcnt(15) (gfx9 encoding)
-template <uint32_t RLOG2, uint32_t LANES, int LOADS = 8>
+template <uint32_t RLOG2, uint32_t LANES>
 __global__ __launch_bounds__(LANES) __attribute__((amdgpu_waves_per_eu(4, 4))) void bin_apply_pipe_kernel(uint32_t* __restrict__ bits, uint64_t nwords,
                                                                uint32_t nbins, const uint32_t* __restrict__ level2,
                                                                const uint32_t* __restrict__ cb_base,
@@ -1407,7 +1406,9 @@ __global__ __launch_bounds__(LANES) __attribute__((amdgpu_waves_per_eu(4, 4))) v
                                                                uint8_t* __restrict__ dirty, uint32_t store_fresh) {
     constexpr uint32_t kVec = 1u << (RLOG2 - 7);   // 16-B vectors per region
     constexpr uint32_t kPer = kVec / LANES;
-    constexpr int kLoads = LOADS;   // (BFHIP_APPLY_PIPE_LOADS A/B)
+    // level-2 loads per lane and gather step: four measured 0.491 / 0.499 against 0.475 / 0.473 ms
+    // (the pipeline prefetches one step: profiles/r04j_ab_apply_pipe_loads.jsonl)
+    constexpr int kLoads = 8;
     constexpr uint32_t kPass = LANES < kRunsPerPass ? LANES : kRunsPerPass;   // run-table entries per pass
     static_assert(kPer * LANES == kVec, "region must tile the workgroup");
     __shared__ uint4 s_mask4[kVec];
@@ -1803,8 +1804,9 @@ constexpr int kL2Loads = 8;
 // 1280 / 1536 / 1792 / 2048 -> test_l2 0.81 / 1.02 / 0.74 / 0.95 / 0.97 ms; P = 4: 0.78 at 1024,
 // 0.72 at 1536 (profiles/r04o8_ab_l2_grid.jsonl, r04n_ab_l2_grid.jsonl, r04p_ab_l2_grid_P4.jsonl)
 constexpr uint32_t kL2Grid = 1536;
+static_assert(kL2Grid % 8 == 0, "whole XCD groups");
 constexpr uint32_t kL2MaxParts = 256;
-template <bool SIDE, bool WALK = true, int LOADS = kL2Loads>
+template <bool SIDE>
 __global__ __launch_bounds__(kL2Lanes) void chunk_test_l2_kernel(BfChunkIn ci, const uint32_t* __restrict__ bits,
                                                                  uint32_t nsup, uint32_t nq, uint32_t parts,
                                                                  const uint32_t* __restrict__ gsum,
@@ -1890,25 +1892,21 @@ __global__ __launch_bounds__(kL2Lanes) void chunk_test_l2_kernel(BfChunkIn ci, c
         __syncthreads();
         const uint32_t h = sb / ci.S, lsb = sb - h * ci.S;
         const uint64_t hoff = (uint64_t)h << 32;
+        constexpr int LOADS = kL2Loads;
         for (uint32_t fb = f0; fb < f1; fb += kL2Lanes * LOADS) {
             uint32_t idx[LOADS], o[LOADS];
-            // WALK: wave v takes LOADS x 64 consecutive entries, one run search for the
-            // wave's first entry, then each lane walks the run table forward (runs of ~40
-            // entries: a step of 64 crosses one or two), instead of a search per entry
+            // wave v takes LOADS x 64 consecutive entries, one run search for the wave's first
+            // entry, then each lane walks the run table forward (runs of ~40 entries: a step of
+            // 64 crosses one or two), instead of a search per entry
             const uint32_t fw = fb + (t >> 6) * (64u * LOADS);
-            uint32_t i = 0;
-            if constexpr (WALK) i = run_of(s_pre, nt, fw < f1 ? fw : f1 - 1);
+            uint32_t i = run_of(s_pre, nt, fw < f1 ? fw : f1 - 1);
 #pragma unroll
             for (int u = 0; u < LOADS; ++u) {
-                const uint32_t f = WALK ? fw + u * 64u + (t & 63u) : fb + u * kL2Lanes + t;
+                const uint32_t f = fw + u * 64u + (t & 63u);
                 idx[u] = 0xFFFFFFFFu;
                 o[u] = 0;
                 if (f < f1) {
-                    if constexpr (WALK) {
-                        while (i + 1 < nt && s_pre[i + 1] <= f) ++i;
-                    } else {
-                        i = run_of(s_pre, nt, f);
-                    }
+                    while (i + 1 < nt && s_pre[i + 1] <= f) ++i;
                     idx[u] = s_gst[i] + (f - s_pre[i]);
                     o[u] = ci.recv[idx[u]];
                 }
@@ -2317,12 +2315,7 @@ hipError_t launch_partition(const BfGeom& g, const BfBinPlan& p, const Carve& c,
     };
     if (dig) {
         if (p.with_keys) return hipErrorInvalidValue;
-        static const bool wide2 = [] {   // A/B: BFHIP_FRONT_WIDE2=0 takes one workgroup per CU
-            const char* e = BF_AB_GETENV("BFHIP_FRONT_WIDE2");
-            return !(e && e[0] == '0');
-        }();
-        if (wide && wide2) front(bin_front_wide_dig_kernel);
-        else if (wide) front(bin_front_wide_kernel<false, true>);
+        if (wide) front(bin_front_wide_dig_kernel);
         else front(bin_front_kernel<true>);
         bf_mark(mk, s, "bin_front_digest");
         return launch_groups_mid(g, p, c, s, mk);
@@ -2429,31 +2422,19 @@ namespace {
 
 // Below the whole-region density, store only the vectors that gain a bit instead of every
 // touched one: 10B@0.01 % step 6.27 ms against 6.43 (profiles/r03m_apply_fresh.jsonl).
-// BFHIP_APPLY_FRESH=0 stores every touched vector (A/B only)
-uint32_t apply_store_fresh() {
-    static const uint32_t v = [] {
-        const char* e = BF_AB_GETENV("BFHIP_APPLY_FRESH");
-        return (uint32_t)!(e && e[0] == '0');
-    }();
-    return v;
-}
+constexpr uint32_t kApplyFresh = 1;
 
 // bin_apply's regions per XCD group (apply_region): 2 measured 2.394 / 2.395 ms against 2.423 /
-// 2.431 (1) and 2.409 / 2.401 (4) at 10B (profiles/r04a_ab_xg.jsonl).  BFHIP_APPLY_XG overrides.
-uint32_t apply_xcd_group() {
-    static const uint32_t v = [] {
-        const char* e = BF_AB_GETENV("BFHIP_APPLY_XG");
-        return (e && e[0]) ? (uint32_t)std::strtoul(e, nullptr, 10) : 2u;
-    }();
-    return v;
-}
+// 2.431 (1) and 2.409 / 2.401 (4) at 10B (profiles/r04a_ab_xg.jsonl).
+constexpr uint32_t kApplyXcdGroup = 2;
+// ... and of the region sets' apply: 2 measured 4.061 / 4.021 ms against 4.115 / 4.128 (1) at
+// 10B x 8 (profiles/r05w_ab_sets_xg.jsonl).
+constexpr uint32_t kSetsXcdGroup = 2;
 
 // Workgroups of the persistent dense apply (bin_apply_pipe_kernel): one per CU (an LDS image
-// plus two run-table buffers; 4 waves per SIMD for its register pipeline).  BFHIP_APPLY_PIPE_GRID=n overrides it; 0 takes bin_apply_kernel (A/B).
+// plus two run-table buffers; 4 waves per SIMD for its register pipeline).
 uint32_t apply_pipe_grid() {
     static const uint32_t v = [] {
-        const char* e = BF_AB_GETENV("BFHIP_APPLY_PIPE_GRID");
-        if (e && e[0]) return (uint32_t)std::strtoul(e, nullptr, 10);
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
@@ -2461,16 +2442,6 @@ uint32_t apply_pipe_grid() {
         return (uint32_t)cus;
     }();
     return v;
-}
-
-// Dense apply form: 1 bin_apply_pipe_kernel, 0 bin_apply_kernel: apply_form_default's choice
-// unless BFHIP_APPLY_FORM (A/B) forces one.
-uint32_t apply_form(uint32_t dense) {
-    static const uint32_t v = [] {
-        const char* e = BF_AB_GETENV("BFHIP_APPLY_FORM");
-        return (e && e[0]) ? (uint32_t)std::strtoul(e, nullptr, 10) : 255u;
-    }();
-    return v != 255u ? v : apply_form_default(dense);
 }
 
 hipError_t launch_apply(const BfGeom& g, const BfBinPlan& p, const Carve& c, uint64_t bitset_bytes,
@@ -2481,38 +2452,20 @@ hipError_t launch_apply(const BfGeom& g, const BfBinPlan& p, const Carve& c, uin
     auto pipe = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(std::min<uint32_t>(p.nbins, pg)), dim3(kPipeLanes), 0, s, g.bits, nwords,
                            p.nbins, c.level2, c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups, p.rel_log2, dense,
-                           any_flag, g.dirty, apply_store_fresh());
+                           any_flag, g.dirty, kApplyFresh);
     };
     auto apply = [&](auto kernel, uint32_t lanes) {
         hipLaunchKernelGGL(kernel, dim3(p.nbins), dim3(lanes), 0, s, g.bits, nwords, c.level2, c.cb_base, c.cb_start,
-                           c.tabs, p.max_chunks, p.ngroups, p.rel_log2, dense, any_flag, g.dirty, apply_store_fresh(),
-                           apply_xcd_group());
+                           c.tabs, p.max_chunks, p.ngroups, p.rel_log2, dense, any_flag, g.dirty, kApplyFresh,
+                           kApplyXcdGroup);
     };
-    if (apply_pipelined(dense, apply_form(dense), p.region_log2, p.nbins, pg)) {
-        [[maybe_unused]] static const int pl = [] {
-            const char* e = BF_AB_GETENV("BFHIP_APPLY_PIPE_LOADS");
-            return e && *e && std::atoi(e) == 4 ? 4 : 8;
-        }();
-#ifdef BFHIP_AB_KNOBS
-        if (pl == 4) pipe(bin_apply_pipe_kernel<19, kPipeLanes, 4>);
-        else
-#endif
-        pipe(bin_apply_pipe_kernel<19, kPipeLanes, 8>);
+    if (apply_pipelined(dense, apply_form_default(dense), p.region_log2, p.nbins, pg)) {
+        pipe(bin_apply_pipe_kernel<19, kPipeLanes>);
     } else if (p.region_log2 == 18) {
         apply(bin_apply_kernel<18, kApplyLanes / 2>, kApplyLanes / 2);
     } else if (p.region_log2 == 19) {
-        // level-2 loads per lane and gather step (region_loads; BFHIP_APPLY_LOADS forces, A/B)
-        static const int forced = [] {
-            const char* e = BF_AB_GETENV("BFHIP_APPLY_LOADS");
-            const int v = e && *e ? std::atoi(e) : 0;
-            return v == 1 || v == 2 || v == 4 || v == 8 ? v : 0;
-        }();
-        const int loads = forced ? forced : region_loads(p.probes, p.nbins);
-        if (loads == 2) apply(bin_apply_kernel<19, kApplyLanes, 2>, kApplyLanes);
-#ifdef BFHIP_AB_KNOBS
-        else if (loads == 1) apply(bin_apply_kernel<19, kApplyLanes, 1>, kApplyLanes);
-        else if (loads == 4) apply(bin_apply_kernel<19, kApplyLanes, 4>, kApplyLanes);
-#endif
+        // level-2 loads per lane and gather step (region_loads)
+        if (region_loads(p.probes, p.nbins) == 2) apply(bin_apply_kernel<19, kApplyLanes, 2>, kApplyLanes);
         else apply(bin_apply_kernel<19, kApplyLanes, 8>, kApplyLanes);
     } else {
         apply(bin_apply_kernel<20, kApplyLanes>, kApplyLanes);
@@ -2524,7 +2477,7 @@ hipError_t launch_apply(const BfGeom& g, const BfBinPlan& p, const Carve& c, uin
 }  // namespace
 
 // The choices launch_partition, launch_scan and launch_apply make for plan p, from the
-// predicates they branch on (the A/B overrides of an -DBFHIP_AB_KNOBS build are not described).
+// predicates they branch on.
 void bf_binned_describe(const BfBinPlan& p, uint32_t k, uint32_t compute_units, bf_plan_detail* out) {
     out->tiles = p.ntiles;
     out->scratch_bytes = p.scratch_bytes;
@@ -2835,9 +2788,6 @@ hipError_t launch_chunk_mid(const BfBinPlan& p, const Carve& c, const BfChunkIn&
     // the group sums also write each window's run table, which the mid's workgroups then read
     // in one coalesced load instead of walking the directories themselves
     uint2* runs = c.runs;
-#ifdef BFHIP_AB_KNOBS
-    if (const char* v = BF_AB_GETENV("BFHIP_MID_RUNS")) runs = atoi(v) ? runs : nullptr;   // (A/B)
-#endif
     hipLaunchKernelGGL(chunk_group_sum_kernel, dim3(p.nsup, p.ngroups), dim3(kRunsPerPass), 0, s, ci, p.ngroups,
                        c.gsum, runs, 0u, (uint16_t*)nullptr);
     launch_scan(p, c, s);
@@ -2849,11 +2799,7 @@ hipError_t launch_chunk_mid(const BfBinPlan& p, const Carve& c, const BfChunkIn&
     // lane-contiguous entries where the shard spans several 2^32-bit sub-ranges: 200B x 8, mids
     // 1.00 / 1.19 -> 0.93 / 1.12 ms; the north star x 8 (one sub-range) keeps the strided form,
     // 0.371 vs 0.393 ms (profiles/r06t_ab_mid_contig.jsonl)
-    bool contig = ci.nh > 1;
-#ifdef BFHIP_AB_KNOBS
-    if (const char* e = BF_AB_GETENV("BFHIP_MID_CONTIG")) contig = e[0] == '1';   // (A/B)
-#endif
-    if (contig) {
+    if (ci.nh > 1) {
         if (p.with_keys) BF_MID_CHUNKS(true, true);
         else BF_MID_CHUNKS(false, true);
     } else if (p.with_keys) {
@@ -2901,7 +2847,7 @@ hipError_t bf_launch_shard_insert_test_chunks_packed(const BfGeom& g, const BfBi
     const int iloads = region_loads(pi.probes, pi.nbins);   // as launch_apply
 #define BF_APPLY_TEST(RL, LANES, LD, SD)                                                                          \
     hipLaunchKernelGGL((bin_apply_test_kernel<RL, LANES, LD, SD>), dim3(pi.nbins), dim3(LANES), 0, s, g.bits, nwords, \
-                       li, lt, pi.rel_log2, dense, any_flag, g.dirty, apply_store_fresh(), ct.ans2, side)
+                       li, lt, pi.rel_log2, dense, any_flag, g.dirty, kApplyFresh, ct.ans2, side)
     const bool sd = side.n != 0;
     if (pi.region_log2 == 18) {   // (a 2^18-bit image cannot hold the side stage: hashed in a pass of its own)
         if (sd) {
@@ -2945,37 +2891,18 @@ hipError_t bf_launch_shard_test_chunks(const BfGeom& g, const BfBinPlan& p, uint
     const Carve c = carve(p, scratch);
     if (p.l2test) {   // no sort: a superbin-major sweep, probes in receive order, answers stored in place
         // each XCD sweeps its own superbins, >= grid / 8 items each (chunk_test_l2_kernel)
-        static const uint32_t grid = [] {
-            const char* e = BF_AB_GETENV("BFHIP_L2_GRID");   // A/B: resident workgroups of the sweep
-            const int v = e ? std::atoi(e) : (int)kL2Grid;
-            return (uint32_t)(v >= 64 && v <= 8192 ? v : (int)kL2Grid) & ~7u;   // whole XCD groups
-        }();
+        constexpr uint32_t grid = kL2Grid;
         // each XCD's grid / 8 workgroups share a superbin's items: at least one item each
         const uint32_t parts = std::min<uint32_t>((grid / 8 + p.ngroups - 1) / p.ngroups, kL2MaxParts);
         hipLaunchKernelGGL(chunk_group_sum_kernel, dim3(p.nsup, p.ngroups), dim3(kRunsPerPass), 0, s, ci, p.ngroups,
                            c.gsum, c.runs, parts, c.istart);
         bf_mark(mk, s, "chunk_group");
-        // entries' runs: one search per wave and a forward walk (1), or a search per entry (0; A/B)
-        [[maybe_unused]] static const bool walk = [] {
-            const char* e = BF_AB_GETENV("BFHIP_L2_WALK");
-            return !(e && *e == '0');
-        }();
-        [[maybe_unused]] static const int l2_loads = [] {
-            const char* e = BF_AB_GETENV("BFHIP_L2_LOADS");
-            return e && *e ? std::atoi(e) : kL2Loads;
-        }();
         auto test = [&](auto kernel) {
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(kL2Lanes), 0, s, ci, g.bits, p.nsup, p.ngroups, parts, c.gsum,
                                c.runs, c.istart, out8, side);
         };
         if (side.n) test(chunk_test_l2_kernel<true>);
-#ifdef BFHIP_AB_KNOBS
-        // (A/B: BFHIP_L2_LOADS, entries per lane in flight)
-        else if (walk && l2_loads == 16) test(chunk_test_l2_kernel<false, true, 16>);
-        else if (walk && l2_loads == 4) test(chunk_test_l2_kernel<false, true, 4>);
-        else if (!walk) test(chunk_test_l2_kernel<false, false>);
-#endif
-        else test(chunk_test_l2_kernel<false, true>);
+        else test(chunk_test_l2_kernel<false>);
         bf_mark(mk, s, side.n ? "test_l2_hash" : "test_l2");
         return hipGetLastError();
     }
@@ -3034,37 +2961,20 @@ hipError_t bf_launch_route_chunks(const BfGeom& g, const BfBinPlan& p, uint32_t 
     // per CU: k > 12 (200B x 8: 0.72 / 0.80 -> 0.62 / 0.66 ms insert / include? route); at k <= 12
     // route_front32's form already runs two and measured the same or 8 % faster (nstar x 8:
     // 0.331 vs 0.357 ms insert route), profiles/r06j_sim_P8.jsonl
-    bool idx = g.k > (uint32_t)kSlots;
-#ifdef BFHIP_AB_KNOBS
-    if (const char* v = BF_AB_GETENV("BFHIP_ROUTE_IDX")) idx = atoi(v) != 0 && (g.k > (uint32_t)kSlots || dig);
-#endif
-    if (idx) {
+    if (g.k > (uint32_t)kSlots) {
         uint32_t* ws = static_cast<uint32_t*>(send);
 #define BF_ROUTE_IDX(KERNEL)                                                                                       \
     hipLaunchKernelGGL(KERNEL, dim3(p.nblocks), dim3(kTile), 0, s, g, keys16, offsets, bias, n, p.tile_keys,          \
                        p.tiles_per_block, p.nsup, wcap, counts, ws, slot16, nh, cg)
-        if (g.k > (uint32_t)kSlots) {
-            if (dig) {
-                if (slot16) BF_ROUTE_IDX((route_chunks_idx_kernel<true, kWideSlots>));
-                else BF_ROUTE_IDX((route_chunks_idx_kernel<false, kWideSlots>));
-            } else if (slot16) BF_ROUTE_IDX((route_chunks_idx_kernel<true, kWideSlots, true>));
-            else BF_ROUTE_IDX((route_chunks_idx_kernel<false, kWideSlots, true>));
-        }
-#ifdef BFHIP_AB_KNOBS
-        else if (slot16) BF_ROUTE_IDX((route_chunks_idx_kernel<true, kSlots>));
-        else BF_ROUTE_IDX((route_chunks_idx_kernel<false, kSlots>));
-#endif
+        if (dig) {
+            if (slot16) BF_ROUTE_IDX((route_chunks_idx_kernel<true, kWideSlots>));
+            else BF_ROUTE_IDX((route_chunks_idx_kernel<false, kWideSlots>));
+        } else if (slot16) BF_ROUTE_IDX((route_chunks_idx_kernel<true, kWideSlots, true>));
+        else BF_ROUTE_IDX((route_chunks_idx_kernel<false, kWideSlots, true>));
 #undef BF_ROUTE_IDX
     } else if (dig) {
-        if (g.k > (uint32_t)kSlots) {
-            if (slot16) BF_ROUTE_CH((route_front_kernel<false, true, kWideSlots, true, true, true>));
-            else BF_ROUTE_CH((route_front_kernel<false, false, kWideSlots, true, true, true>));
-        }
-        else if (slot16) BF_ROUTE_CH((route_front32_kernel<true, true, true, true>));
+        if (slot16) BF_ROUTE_CH((route_front32_kernel<true, true, true, true>));
         else BF_ROUTE_CH((route_front32_kernel<false, true, true, true>));
-    } else if (g.k > (uint32_t)kSlots) {
-        if (slot16) BF_ROUTE_CH((route_front_kernel<false, true, kWideSlots, true, true>));
-        else BF_ROUTE_CH((route_front_kernel<false, false, kWideSlots, true, true>));
     }
     else if (slot16) BF_ROUTE_CH((route_front32_kernel<true, true, true>));
     else BF_ROUTE_CH((route_front32_kernel<false, true, true>));
@@ -3228,7 +3138,7 @@ __device__ __forceinline__ void sets_encode_region(uint32_t r, uint32_t nbins, c
                                                    const uint16_t* __restrict__ tabs, uint64_t max_chunks,
                                                    uint32_t nq, uint32_t rel_log2, uint32_t* __restrict__ out,
                                                    const uint32_t* __restrict__ sb_first, uint32_t cap_words,
-                                                   uint32_t stop, uint4* s_m4, uint32_t* s_runs, uint32_t* s_w) {
+                                                   uint4* s_m4, uint32_t* s_runs, uint32_t* s_w) {
     constexpr uint32_t U = 1u << RLOG2, NW = U / 32, WPL = NW / LANES;
     static_assert(WPL * LANES == NW && WPL % 4 == 0 && WPL <= 32, "region words must tile the lanes in vectors");
     constexpr uint32_t kSetLds = 5u * NW / 32u + 2u * NW / 32u + 2u;
@@ -3243,12 +3153,6 @@ __device__ __forceinline__ void sets_encode_region(uint32_t r, uint32_t nbins, c
     for (uint32_t v = t; v < NW / 4; v += LANES) s_m4[v] = make_uint4(0, 0, 0, 0);
     __syncthreads();
     if (!(rv & 0x80000000u)) return;   // workgroup-uniform: no probes (out[4 + r] is already 0)
-#ifdef BFHIP_AB_KNOBS
-    if (stop == 3) {   // (A/B: where the time goes; BFHIP_SETS_STOP) the region left absent
-        if (t == 0) out[kSetsHdr + r] = out[kSetsHdr + nbins + r] = 0;   // every lane read rv before the barrier
-        return;
-    }
-#endif
     const uint32_t st = sbf + (rv & 0x7FFFFFFFu);
     // LOADS level-2 loads per lane and step: a region's ~2k probes over all 16 waves (2), or
     // over 4 of them with more loads in flight each (8)
@@ -3261,12 +3165,6 @@ __device__ __forceinline__ void sets_encode_region(uint32_t r, uint32_t nbins, c
             for (int c = 0; c < LOADS; ++c)
                 if (l[c] != 0xFFFFFFFFu) atomicOr(s_m + (l[c] >> 5), 1u << ((l[c] ^ 7u) & 31u));
         });
-#ifdef BFHIP_AB_KNOBS
-    if (stop == 2) {   // (A/B)
-        if (t == 0) out[kSetsHdr + r] = out[kSetsHdr + nbins + r] = 0;
-        return;
-    }
-#endif
     // the run table is dead (for_region_probes ends on a barrier): a sparse set's image is
     // cleared; the scan's barriers below order these stores before its first atomic
     for (uint32_t v = t; v < kSetLds; v += LANES) s_set[v] = 0;
@@ -3300,14 +3198,6 @@ __device__ __forceinline__ void sets_encode_region(uint32_t r, uint32_t nbins, c
     }
     if (!fits) return;   // workgroup-uniform
     uint32_t* o = out + st;
-#ifdef BFHIP_AB_KNOBS
-    if (stop == 1) {   // (A/B) the region left absent, so no reader decodes the unwritten set
-        if (t == 0) out[kSetsHdr + r] = out[kSetsHdr + nbins + r] = 0;
-        return;
-    }
-#else
-    (void)stop;
-#endif
     if (bitmap) {   // the LDS bitmap is still intact
         if (t == 0) o[0] = n | (kSetsBitmap << 24);
         for (uint32_t v = t; v < NW; v += LANES) o[1 + v] = s_m[v];
@@ -3361,12 +3251,11 @@ __global__ __launch_bounds__(LANES) __attribute__((amdgpu_waves_per_eu(2 * LANES
                                                             const uint32_t* __restrict__ cb_start,
                                                             const uint16_t* __restrict__ tabs, uint64_t max_chunks,
                                                             uint32_t nq, uint32_t rel_log2, uint32_t* __restrict__ out,
-                                                            const uint32_t* __restrict__ sb_first, uint32_t cap_words,
-                                                            uint32_t stop) {
+                                                            const uint32_t* __restrict__ sb_first, uint32_t cap_words) {
     __shared__ uint4 s_m4[(1u << RLOG2) / 128];
     __shared__ uint32_t s_runs[sets_encode_run_lds<RLOG2>()], s_w[16];
     sets_encode_region<RLOG2, LANES, LOADS>(blockIdx.x, gridDim.x, level2, cb_base, cb_start, tabs, max_chunks, nq,
-                                            rel_log2, out, sb_first, cap_words, stop, s_m4, s_runs, s_w);
+                                            rel_log2, out, sb_first, cap_words, s_m4, s_runs, s_w);
 }
 
 // One workgroup per region: every source's set for the region ORed into an LDS image (bitmap
@@ -3391,7 +3280,7 @@ void sets_encode_persistent_kernel(const uint32_t* __restrict__ level2, const ui
     __shared__ uint32_t s_runs[sets_encode_run_lds<RLOG2>()], s_w[16];
     for (uint32_t r = blockIdx.x; r < nbins; r += gridDim.x) {
         sets_encode_region<RLOG2, LANES, LOADS>(r, nbins, level2, cb_base, cb_start, tabs, max_chunks, nq, rel_log2,
-                                                out, sb_first, cap_words, 0u, s_m4, s_runs, s_w);
+                                                out, sb_first, cap_words, s_m4, s_runs, s_w);
         __syncthreads();   // every lane is past the region's LDS before the next one clears it
     }
 }
@@ -3617,22 +3506,9 @@ void sets_apply_encode_kernel(uint32_t* __restrict__ bits, uint64_t nwords, cons
                                            store_fresh, status, s_mask4, s_lows, s_tabs);
     __syncthreads();   // the image and the stage are reused by the encode
     sets_encode_region<RLOG2, LANES, LOADS>(r, nbins, level2, cb_base, cb_start, tabs, max_chunks, nq, rel_log2, out,
-                                            sb_first, cap_words, 0u, s_mask4, s_lows, s_tabs.w);
+                                            sb_first, cap_words, s_mask4, s_lows, s_tabs.w);
 }
 
-}  // namespace
-
-namespace {
-// A/B only (BFHIP_SETS_STOP, -DBFHIP_AB_KNOBS builds): the encode stops after its probe pass
-// (2), before writing the set (1), or at once (3); the output is then incomplete.  0: the whole
-// encode (the shipped library has no stop points at all).
-uint32_t sets_stop() {
-    static const uint32_t v = [] {
-        const char* e = BF_AB_GETENV("BFHIP_SETS_STOP");
-        return (e && e[0]) ? (uint32_t)std::strtoul(e, nullptr, 10) : 0u;
-    }();
-    return v;
-}
 }  // namespace
 
 uint64_t bf_sets_header_words(uint32_t nbins) { return sets_first_word(nbins); }
@@ -3683,24 +3559,17 @@ hipError_t bf_launch_encode_sets(const BfGeom& g, const BfBinPlan& p, uint64_t b
     // over all 16 waves) up to 4096 probes per region on average, else 8.  10B (~2k per region):
     // 2.85 (2) / 2.94 (4) / 3.26 (8) ms, r04 encode; north star x 2 (~5.5k): 0.552 / 0.546 (2),
     // 0.532 / 0.517 (4), 0.520 / 0.520 (8) ms (profiles/r04h_ab_sets_enc_loads.jsonl,
-    // r05w_ab_sets_enc_loads_nstar.jsonl).  BFHIP_SETS_ENC_LOADS (A/B) forces 1, 2, 4 or 8.
-    static const int forced = [] {
-        const char* e = BF_AB_GETENV("BFHIP_SETS_ENC_LOADS");
-        const int v = e && *e ? std::atoi(e) : 0;
-        return v == 8 || v == 4 || v == 2 || v == 1 ? v : 0;
-    }();
-    const int loads = forced ? forced : region_loads(n * g.k, p.nbins);
-    uint32_t enc_grid = persistent_grid;
-#ifdef BFHIP_AB_KNOBS
-    if (const char* e = BF_AB_GETENV("BFHIP_SETS_ENC_GRID")) enc_grid = (uint32_t)std::strtoul(e, nullptr, 10);   // (A/B)
-#endif
-    if (enc_grid && p.region_log2 == 19) {
+    // r05w_ab_sets_enc_loads_nstar.jsonl).
+    const int loads = region_loads(n * g.k, p.nbins);
+    if (persistent_grid && p.region_log2 == 19) {
         if (loads == 8)
-            hipLaunchKernelGGL((sets_encode_persistent_kernel<19, kApplyLanes, 8>), dim3(enc_grid), dim3(kApplyLanes),
+            hipLaunchKernelGGL((sets_encode_persistent_kernel<19, kApplyLanes, 8>), dim3(persistent_grid),
+                               dim3(kApplyLanes),
                                0, s, c.level2, c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups, p.rel_log2, out,
                                c.stot, (uint32_t)cap_words, p.nbins);
         else
-            hipLaunchKernelGGL((sets_encode_persistent_kernel<19, kApplyLanes, 2>), dim3(enc_grid), dim3(kApplyLanes),
+            hipLaunchKernelGGL((sets_encode_persistent_kernel<19, kApplyLanes, 2>), dim3(persistent_grid),
+                               dim3(kApplyLanes),
                                0, s, c.level2, c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups, p.rel_log2, out,
                                c.stot, (uint32_t)cap_words, p.nbins);
         bf_mark(mk, s, "sets_encode");
@@ -3708,20 +3577,12 @@ hipError_t bf_launch_encode_sets(const BfGeom& g, const BfBinPlan& p, uint64_t b
     }
 #define BF_SETS_ENCODE(RL, LN, LD)                                                                              \
     hipLaunchKernelGGL((sets_encode_kernel<RL, LN, LD>), dim3(p.nbins), dim3(LN), 0, s, c.level2, c.cb_base,    \
-                       c.cb_start, c.tabs, p.max_chunks, p.ngroups, p.rel_log2, out, c.stot, (uint32_t)cap_words, \
-                       sets_stop())
+                       c.cb_start, c.tabs, p.max_chunks, p.ngroups, p.rel_log2, out, c.stot, (uint32_t)cap_words)
     if (p.region_log2 == 19) {
         if (loads == 8) BF_SETS_ENCODE(19, kApplyLanes, 8);
-#ifdef BFHIP_AB_KNOBS
-        else if (loads == 4) BF_SETS_ENCODE(19, kApplyLanes, 4);
-        else if (loads == 1) BF_SETS_ENCODE(19, kApplyLanes, 1);
-#endif
         else BF_SETS_ENCODE(19, kApplyLanes, 2);
     } else if (p.region_log2 == 18) {
         if (loads == 8) BF_SETS_ENCODE(18, kApplyLanes / 2, 8);
-#ifdef BFHIP_AB_KNOBS
-        else if (loads == 4) BF_SETS_ENCODE(18, kApplyLanes / 2, 4);
-#endif
         else BF_SETS_ENCODE(18, kApplyLanes / 2, 2);
     } else {
         return hipErrorInvalidValue;
@@ -3737,36 +3598,18 @@ hipError_t bf_launch_insert_sets(const BfGeom& g, uint64_t bitset_bytes, uint32_
     if (nsrc == 0) return hipSuccess;
     const uint64_t nwords = bitset_bytes / 4;
     const uint32_t dense = probe_density(probes_hint, nbins, region_log2);
-    // low-bit stage: 1 (default) 15 KB at 2^19-bit regions (two workgroups per CU), 7.5 KB at
-    // 2^18; 0: none (A/B; a 48-KB stage at one workgroup per CU measured 7.07 against 4.72 ms
-    // at 10B, profiles/r04g_ab_sets_stage.jsonl)
-    [[maybe_unused]] static const uint32_t stage = [] {
-        const char* e = BF_AB_GETENV("BFHIP_SETS_STAGE");
-        return e && *e ? (uint32_t)std::strtoul(e, nullptr, 10) : 1u;
-    }();
-    // regions per XCD group (apply_region, as bin_apply): 2 measured 4.061 / 4.021 ms against
-    // 4.115 / 4.128 (1) at 10B x 8 (profiles/r05w_ab_sets_xg.jsonl).  BFHIP_SETS_XG (A/B) overrides.
-    static const uint32_t sets_xg = [] {
-        const char* e = BF_AB_GETENV("BFHIP_SETS_XG");
-        return e && *e ? (uint32_t)std::strtoul(e, nullptr, 10) : 2u;
-    }();
+    // low-bit stage (kLowsStage): 15 KB at 2^19-bit regions (two workgroups per CU), 7.5 KB at
+    // 2^18 (a 48-KB stage at one workgroup per CU measured 7.07 against 4.72 ms at 10B,
+    // profiles/r04g_ab_sets_stage.jsonl)
     for (uint32_t s0 = 0; s0 < nsrc; s0 += kMaxSetSrc) {
         const uint32_t ns = std::min<uint32_t>(kMaxSetSrc, nsrc - s0);
         const uint32_t* src = sets + (uint64_t)s0 * stride_words;
 #define BF_SETS_APPLY(RL, LN, ST)                                                                              \
     hipLaunchKernelGGL((sets_apply_kernel<RL, LN, ST>), dim3(nbins), dim3(LN), 0, s, g.bits, nwords, src,       \
-                       stride_words, ns, nbins, dense, any_flag, g.dirty, apply_store_fresh(), status, sets_xg)
+                       stride_words, ns, nbins, dense, any_flag, g.dirty, kApplyFresh, status, kSetsXcdGroup)
         if (region_log2 == 19) {
-#ifdef BFHIP_AB_KNOBS
-            if (stage == 0) BF_SETS_APPLY(19, kApplyLanes, 0);
-            else
-#endif
             BF_SETS_APPLY(19, kApplyLanes, kLowsStage);
         } else if (region_log2 == 18) {
-#ifdef BFHIP_AB_KNOBS
-            if (stage == 0) BF_SETS_APPLY(18, kApplyLanes / 2, 0);
-            else
-#endif
             BF_SETS_APPLY(18, kApplyLanes / 2, kLowsStage / 2);
         } else {
             return hipErrorInvalidValue;
@@ -3783,11 +3626,8 @@ hipError_t bf_launch_insert_encode_sets(const BfGeom& g, const BfBinPlan& p, uin
                                         uint32_t* status, const uint8_t* next_dig, uint64_t n_next, void* scratch,
                                         uint32_t* next_out, uint64_t cap_words, hipStream_t s, BfMarks* mk) {
     if (cap_words >= (1ull << 32)) return hipErrorInvalidValue;
-    bool fuse = n_next && nsrc && nsrc <= kMaxSetSrc && !p.with_keys && p.region_log2 == region_log2 &&
+    const bool fuse = n_next && nsrc && nsrc <= kMaxSetSrc && !p.with_keys && p.region_log2 == region_log2 &&
                 p.nbins == nbins && (region_log2 == 19 || region_log2 == 18);
-#ifdef BFHIP_AB_KNOBS
-    if (const char* v = BF_AB_GETENV("BFHIP_SETS_FUSE")) fuse = fuse && atoi(v) != 0;   // (A/B: 0 = two kernels)
-#endif
     if (!fuse) {   // the next batch's encode (no bitset read), then the apply: the two calls in order
         hipError_t e = bf_launch_encode_sets(g, p, bitset_bytes, next_dig, nullptr, 0, n_next, true, scratch, next_out,
                                              cap_words, s, mk);
@@ -3804,12 +3644,11 @@ hipError_t bf_launch_insert_encode_sets(const BfGeom& g, const BfBinPlan& p, uin
     const int loads = region_loads(n_next * g.k, p.nbins);   // as bf_launch_encode_sets
     const uint64_t nwords = bitset_bytes / 4;
     const uint32_t dense = probe_density(probes_hint, nbins, region_log2);
-    const uint32_t xg = 2u;   // as bf_launch_insert_sets
 #define BF_SETS_APPLY_ENCODE(RL, LN, ST, LD)                                                                     \
     hipLaunchKernelGGL((sets_apply_encode_kernel<RL, LN, ST, LD>), dim3(nbins), dim3(LN), 0, s, g.bits, nwords, sets, \
-                       stride_words, nsrc, nbins, dense, any_flag, g.dirty, apply_store_fresh(), status, xg, c.level2,  \
-                       c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups, p.rel_log2, next_out, c.stot,           \
-                       (uint32_t)cap_words)
+                       stride_words, nsrc, nbins, dense, any_flag, g.dirty, kApplyFresh, status, kSetsXcdGroup,   \
+                       c.level2, c.cb_base, c.cb_start, c.tabs, p.max_chunks, p.ngroups, p.rel_log2, next_out,  \
+                       c.stot, (uint32_t)cap_words)
     if (region_log2 == 19) {
         if (loads == 8) BF_SETS_APPLY_ENCODE(19, kApplyLanes, kLowsStage, 8);
         else BF_SETS_APPLY_ENCODE(19, kApplyLanes, kLowsStage, 2);

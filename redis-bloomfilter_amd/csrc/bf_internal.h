@@ -11,6 +11,8 @@
 // shipped library takes the measured defaults: the names are not even in its strings, so no
 // inherited variable can change what it computes or how (tests/test_abi.py checks the list).
 // The knobs a test uses to force a path (all of which give identical results) stay readable.
+// A knob lives only while its experiment is open: once §6f records the verdict, the knob, its
+// dispatch and the rejected variant leave the tree.
 #ifdef BFHIP_AB_KNOBS
 #define BF_AB_GETENV(name) std::getenv(name)
 #else

@@ -158,9 +158,9 @@ def test_library_is_gfx950_only(pkg):
 
 
 # The only environment knobs the shipped library reads: path choices the GPU tests force (every
-# one gives identical results) and the host staging thread count.  The A/B knobs of DESIGN §6f,
-# including the encode stop points that write incomplete region sets, exist only in
-# -DBFHIP_AB_KNOBS builds (tools/build_ab_libs.sh) — VERDICT r04 item 2.
+# one gives identical results) and the host staging thread count.  An experiment's A/B knob
+# (BF_AB_GETENV / ab_u32) exists only in -DBFHIP_AB_KNOBS builds (tools/build_ab_libs.sh) and
+# leaves the tree once DESIGN §6f records its verdict — VERDICT r04 item 2.
 PRODUCT_KNOBS = {"BFHIP_INSERT_BINNED", "BFHIP_INCLUDE_BINNED", "BFHIP_BIN_REGION_LOG2",
                  "BFHIP_SHARD_TEST_BINNED", "BFHIP_CHUNK_TEST_L2", "BFHIP_ROUTE_AGG", "BFHIP_HOST_THREADS"}
 

@@ -4,8 +4,8 @@
 set -e
 cd "$(dirname "$0")/.."
 # Variants: NAME=FLAGS pairs, e.g. bash tools/build_ab_libs.sh v1=-DMY_KNOB=1 (the r01 knobs are folded in).
-# The environment A/B knobs of DESIGN §6f (BFHIP_APPLY_*, BFHIP_SETS_*, BFHIP_L2_*, ...) are
-# compiled only with -DBFHIP_AB_KNOBS: bash tools/build_ab_libs.sh ab=-DBFHIP_AB_KNOBS
+# An open experiment's environment knobs (BF_AB_GETENV, ab_u32) are compiled only with
+# -DBFHIP_AB_KNOBS: bash tools/build_ab_libs.sh ab=-DBFHIP_AB_KNOBS
 for nv in "$@"; do
     for pair in $nv; do
         make -s -j8 -C redis-bloomfilter_amd/csrc OUTDIR=$PWD/ab_libs/${pair%%=*} EXTRA="${pair#*=}"

@@ -485,8 +485,7 @@ def replicated(args, pkg):
         for name, (ms, n) in enc.profile_read(reset=True).items():
             prof["side:" + name] = (ms, n)
         enc.close()
-    if os.environ.get("BFHIP_SETS_STOP", "0") == "0":   # (the encode stop-point A/B writes no sets)
-        assert out.cpu().numpy()[: batch // 2].all(), "false negative"
+    assert out.cpu().numpy()[: batch // 2].all(), "false negative"
     res = {"config": args.config, "layout": "replicated", "world": R, "gathered": args.gathered,
            "fused_hash": bool(args.fused_hash), "overlap_encode": ovl or None,
            "main_priority": bool(ovl and args.main_priority), "side_priority": bool(ovl and args.side_priority),
